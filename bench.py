@@ -23,12 +23,18 @@ HBM before the timed region starts.  Before the W warm-up steps the primary work
 Workload: BASELINE.json configs[2] -- ~1.1 M SNPs in ~1 700 LD blocks (lognormal block sizes, SURVEY.md 8d;
 long-range non-Toeplitz block LD by default, `--ld-kind ar1` for the analytic AR(1) blocks of rounds 1-2),
 spike-and-slab prior, fp32 state, fp32 LD in the reference's DEFAULT form (upper-triangular, `low_memory=True`; `--symmetric`
-selects the other, which is also the first secondary and is repeated at the top level as `symmetric_ld_form`).  N = 1 also
-times, as `config.secondary`, configs[3] (mixture K = 4) and configs[4] (grid of 32 models) on the same resident LD in both
-forms, the int8 store format, a float64 state, math_mode=fast, the EM iteration of the three models, the reference's
-default OPERATING mode (22 per-chromosome models: one lock-step batch against 22 fits one after the other) and
-BASELINE configs[0] / configs[1] with the CPU baseline of their own workloads.  `metric_definition` stamps what `value`
+selects the other, which with --full is also the first secondary and is repeated at the top level as `symmetric_ld_form`).
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs (`--dump-outputs DIR`) and
+the line.  Everything else runs only with `--full`: N = 1 then also times, as `config.secondary`, configs[3] (mixture K = 4)
+and configs[4] (grid of 32 models) on the same resident LD in both forms, the int8 store format, a float64 state,
+math_mode=fast, the EM iteration of the three models, the reference's default OPERATING mode (22 per-chromosome models: one
+lock-step batch against 22 fits one after the other), BASELINE configs[0] / configs[1] with the CPU baseline of their own
+workloads, the measured chain step (`config.chain_ns_per_snp`) and the CPU baseline of the headline workload
+(`cpu_baseline`); N > 1 the other scaling figure.  `metric_definition` stamps what `value`
 is (LD form, scaling mode, state placement) so that lines of different rounds are compared like for like.
+`--dump-outputs DIR`: the state the last timed step left (var_gamma, var_mu, eta, q, eta_diff: what a caller of the E-step
+receives) as DIR/<name>.npy, at most 64 MB in all -- beyond that the same seeded sample of SNPs from every array, whose row
+numbers are DIR/sample_rows.npy; N > 1: every rank its own share, DIR/<name>_rank<r>.npy.
 N > 1 (default, "strong" = BASELINE.json configs[2], "block-sharded 1/2/4/8 GPUs"): the blocks of ONE 1.1 M-SNP /
 1 700-block workload are dealt to the ranks (chain-aware LPT, viprs_amd.parallel.shard_blocks; no data-path
 collective) and `value` = that workload's SNPs per max-over-ranks sweep time -- the same quantity as the N = 1 line.
@@ -77,10 +83,16 @@ def parse_args():
                          "one genome-scale workload per rank (N x the work).  The other figure is measured beside `value` in the same run")
     ap.add_argument("--host-ld", action="store_true",
                     help="build every synthetic LD array on the host and upload it (default: on the device, except the N = 1 "
-                         "headline workload, which the CPU baseline needs on the host)")
+                         "headline workload of a --full run, which the CPU baseline needs on the host)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the secondary measurements, the chain-step probe and the "
+                         "CPU baseline (a plain run sets up, warms up, times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left as DIR/<name>.npy (at most 64 MB in all: beyond that a "
+                         "fixed, seeded sample of SNPs, DIR/sample_rows.npy)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements (N = 1: upper-triangular sweep; N > 1: weak scaling)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg (0 = skip)")
+                    help="with --full: skip the secondary measurements (N = 1: upper-triangular sweep; N > 1: weak scaling)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="with --full: budget of the CPU baseline leg (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the multi-threaded CPU variants (default: affinity mask capped by the cgroup quota)")
     ap.add_argument("--model", default="spike_slab", choices=["spike_slab", "mixture", "grid"],
@@ -95,6 +107,8 @@ def parse_args():
                          "run 2 %% slower: clocks and TLBs; a fit runs hundreds of iterations); reported as config.prewarm_s")
     ap.add_argument("--seed", type=int, default=7209)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.symmetric and args.low_memory:
         ap.error("--symmetric and --low-memory exclude each other")
     args.low_memory = not args.symmetric
@@ -381,6 +395,31 @@ class Sweep:
         self.state.close()
         if self.own_plan:
             self.plan.close()
+
+
+OUTPUTS = ("var_gamma", "var_mu", "eta", "q", "eta_diff")      # what the E-step hands back to its caller
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES, suffix=""):
+    """Writes `arrays` (name -> float32 / float64 array with one row per SNP) as DIR/<name><suffix>.npy.  Over `budget` bytes
+    in all, every array keeps the same rows: a fixed, seeded sample in SNP order, whose row numbers are written as
+    DIR/sample_rows<suffix>.npy (float64).  Returns the names written."""
+    os.makedirs(directory, exist_ok=True)
+    m = len(next(iter(arrays.values())))
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64) or len(a) != m:
+            raise ValueError(f"dump_outputs: {name} is {a.dtype} with {len(a)} rows, expected float32 / float64 with {m}")
+    row_bytes = sum(a.nbytes // max(1, m) for a in arrays.values())
+    if row_bytes * m > budget:
+        n = max(1, int(budget // (row_bytes + 8)))                          # (+ 8: the row number itself)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(m, size=n, replace=False))
+        arrays = {k: np.ascontiguousarray(a[rows]) for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def pct(v, q):
@@ -904,8 +943,8 @@ def main():
     t_start = time.perf_counter()
     strong = world > 1 and args.scaling == "strong"
     # LD entries: on the device for every rank of a multi-GPU run; the N = 1 headline workload on the host (the CPU
-    # baseline and the fit() secondaries run on the host arrays) unless neither is asked for (profiling runs)
-    on_host = world == 1 and (args.cpu_seconds > 0 or not args.no_secondary or args.host_ld)
+    # baseline and the fit() secondaries run on the host arrays) unless neither is asked for (plain and profiling runs)
+    on_host = world == 1 and (args.host_ld or (args.full and (args.cpu_seconds > 0 or not args.no_secondary)))
     if strong:
         parts = shard_blocks_lpt(sizes_all, world)
         mine = parts[rank]
@@ -925,6 +964,9 @@ def main():
                 sw.step()
             sw.state.synchronize()
     my_elapsed = sw.run(args.steps, args.warmup, barrier)
+    if args.dump_outputs:                                 # (before anything else sweeps on this state)
+        dump_outputs(args.dump_outputs, {k: sw.state.download(k) for k in OUTPUTS}, DUMP_BUDGET_BYTES // world,
+                     f"_rank{rank}" if world > 1 else "")
     elapsed = float(comm.allreduce_max(np.array([my_elapsed]))[0])
     skipped = sw.plan.last_skipped()
     sw_math_effective = sw.plan.effective_math_mode() if hasattr(sw.plan, "effective_math_mode") else None
@@ -948,13 +990,13 @@ def main():
     model_ms = float(np.max(model_ranks))
 
     chain_ns = None
-    if world == 1 and args.model == "spike_slab" and args.precision == "float32" and not args.no_secondary:
+    if args.full and world == 1 and args.model == "spike_slab" and args.precision == "float32" and not args.no_secondary:
         chain_ns = chain_ns_per_snp(args, device, args.math, args.low_memory)     # isolated 6 000-SNP block
 
-    # ---- secondary measurements -----------------------------------------------------------------------------
+    # ---- secondary measurements (--full) ---------------------------------------------------------------------
     secondary = []
     weak = None
-    if not args.no_secondary and args.model == "spike_slab" and args.precision == "float32":
+    if args.full and not args.no_secondary and args.model == "spike_slab" and args.precision == "float32":
         half = max(5, args.steps // 2)
         if world == 1 and args.low_memory and args.ld_dtype == "float32" and args.config != "cfg1":
             # `value` is the reference's DEFAULT LD form (low_memory=True, VIPRS.py:75: the upper-triangular store, swept over
@@ -1111,6 +1153,7 @@ def main():
                                 if strong else f"one workload per GPU x{n_gpus}") if n_gpus > 1 else "single GPU",
                 "step": "device state re-init + one E-step sweep over all blocks",
                 "prewarm_s": args.prewarm_seconds,        # untimed sweeps before the W warm-up steps (steady-state clocks)
+                "full": bool(args.full),                  # secondaries, chain-step probe and CPU baseline were measured
                 # where the state's per-SNP arrays were put: best of n allocations by a probe sweep (viprs_amd/plan.py)
                 "state_placement": getattr(sw.state, "placement", None),
                 "time_model_ms": model_ms,
@@ -1190,7 +1233,7 @@ def main():
                                       "ld_entries": "generated on the device" if ld.ld_data is None else "built on the host, uploaded"}
         if weak is not None:
             out["weak_scaling" if strong else "strong_scaling"] = weak
-        if n_gpus == 1 and args.cpu_seconds > 0 and args.precision == "float32":
+        if args.full and n_gpus == 1 and args.cpu_seconds > 0 and args.precision == "float32":
             out["cpu_baseline"] = cpu_baseline(ld, inp, args.cpu_seconds, args.model, width, sw.host_extra, sw.pi0,
                                                args.cpu_threads)
         print(json.dumps(out), flush=True)

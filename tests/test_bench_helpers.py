@@ -147,7 +147,7 @@ print("RANK_DONE", os.environ["RANK"])
 """
 
 
-@pytest.mark.parametrize("extra", [[], ["--scaling", "weak"]], ids=["strong-default", "weak"])
+@pytest.mark.parametrize("extra", [["--full"], ["--full", "--scaling", "weak"]], ids=["strong-default", "weak"])
 def test_bench_main_two_ranks_end_to_end_over_the_file_transport(tmp_path, extra):
     """bench.py's N > 1 path run for real with two processes (torch.distributed.run-style environment,
     VIPRS_BENCH_COMM=file, device layer stubbed): ONE JSON line from rank 0 whose `n_gpus`, `comm`, `snps_total`,
@@ -217,6 +217,7 @@ _SITE_STUB = r"""
 import os, sys, time
 if "RANK" in os.environ:
     sys.path.insert(0, {root!r})
+    import numpy as np
     from viprs_amd import _lib, plan as plan_mod
     _lib.device_count = lambda: {ndev}
     class _FakeLib:
@@ -240,6 +241,7 @@ if "RANK" in os.environ:
         def upload(self, name, arr): assert arr.shape[0] == self.plan.m
         def reset(self, pi): pass
         def e_step(self, dq, active=None, sync=True): self.plan.n += 1; time.sleep(0.001)
+        def download(self, name): return np.arange(self.plan.m, dtype=np.float32) + len(name)
         def synchronize(self): pass
         def close(self): pass
     plan_mod.LDPlan, plan_mod.DeviceState = FakePlan, FakeState
@@ -263,8 +265,8 @@ def test_bare_bench_gpus_2_starts_two_ranks_itself(tmp_path):
     """`python bench.py --gpus 2` without WORLD_SIZE must not run ONE process and print n_gpus 2 -- the
     parent starts two fresh rank processes, relays rank 0's single line, and the line shows both ranks took part."""
     import json
-    r = _run_bare_bench(tmp_path, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "cfg2", "--cpu-seconds", "0"],
-                        ndev=2, env_extra={"VIPRS_BENCH_COMM": "file"})
+    r = _run_bare_bench(tmp_path, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "cfg2", "--cpu-seconds", "0",
+                                   "--full"], ndev=2, env_extra={"VIPRS_BENCH_COMM": "file"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
@@ -346,3 +348,59 @@ def test_clean_kernel_times_uses_the_host_stamp_not_the_kernel_time():
     assert bad == [0, 1] and good == [0.6946, 0.7016, 1.9, 0.6925]          # the 1.9 ms sweep has no host time: it stays
     assert bench.clean_kernel_times(k, []) == (k, [])                        # no stamps (older library): nothing is dropped
     assert bench.clean_kernel_times([0.7, 0.7], [0.5, 0.6]) == ([0.7, 0.7], [0, 1])      # never an empty mean
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` does only what the headline needs: exactly K timed steps, the line
+    with its headline fields and nothing of --full (secondaries, chain-step probe, CPU baseline); `--dump-outputs DIR`
+    writes what the last timed step left, one float32 / float64 .npy per E-step output."""
+    import json
+    import os
+    out_dir = tmp_path / "out"
+    r = _run_bare_bench(tmp_path, ["--gpus", "1", "--steps", "4", "--warmup", "1", "--config", "cfg2", "--prewarm-seconds", "0",
+                                   "--dump-outputs", str(out_dir)],
+                        ndev=1, env_extra={"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{") and len(lines[0]) < 8192, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    sizes = bench.config_sizes("cfg2", 7209)
+    assert out["metric"] == "SNP-updates/sec/E-step (1M SNPs, ~1700 LD blocks)" and out["unit"] == "SNP-updates/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["n_gpus"] == 1
+    assert out["steps"] == 4 and out["warmup"] == 1
+    assert out["value"] == pytest.approx(int(sizes.sum()) / (out["ms_per_step"] * 1e-3), rel=1e-6)
+    assert len(out["roofline"]["kernel_ms_all"]) == 4                       # the timed steps, no more
+    assert out["config"]["full"] is False and out["config"]["secondary"] is None
+    assert out["config"]["chain_ns_per_snp"] is None and "cpu_baseline" not in out and "symmetric_ld_form" not in out
+    assert sorted(os.listdir(out_dir)) == sorted(f"{k}.npy" for k in bench.OUTPUTS)
+    for k in bench.OUTPUTS:
+        a = np.load(out_dir / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == (int(sizes.sum()),)
+        np.testing.assert_array_equal(a, np.arange(a.size, dtype=np.float32) + len(k))     # the stub's download
+
+
+def test_dump_outputs_keeps_the_same_seeded_rows_of_every_array_within_the_budget(tmp_path):
+    m = 1000
+    rng = np.random.default_rng(1)
+    arrays = {"a": rng.standard_normal(m).astype(np.float32), "b": rng.standard_normal((m, 4)),
+              "c": np.asfortranarray(rng.standard_normal((m, 3)).astype(np.float32))}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == ["a", "b", "c"]
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "all" / f"{k}.npy"), v)
+    budget = 20_000
+    names = bench.dump_outputs(str(tmp_path / "s1"), arrays, budget=budget, suffix="_rank1")
+    assert names == ["a", "b", "c", "sample_rows"]
+    files = {k: tmp_path / "s1" / f"{k}_rank1.npy" for k in names}
+    assert sum(np.load(f).nbytes for f in files.values()) <= budget
+    rows = np.load(files["sample_rows"])
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and rows.size == budget // (4 + 32 + 12 + 8)
+    idx = rows.astype(np.int64)
+    for k, v in arrays.items():
+        got = np.load(files[k])
+        assert got.dtype == v.dtype
+        np.testing.assert_array_equal(got, v[idx])
+    bench.dump_outputs(str(tmp_path / "s2"), arrays, budget=budget, suffix="_rank1")     # the same sample, run to run
+    for k in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "s2" / f"{k}_rank1.npy"), np.load(files[k]))
+    with pytest.raises(ValueError, match="float32 / float64"):
+        bench.dump_outputs(str(tmp_path / "bad"), {"i": np.arange(m)})

@@ -1,4 +1,4 @@
-"""Prints the headline, the secondaries and the CPU baseline of a bench.py JSON line.
+"""Prints the headline, the secondaries and the CPU baseline of a `bench.py --full` JSON line.
     python tools/show_bench.py bench.json"""
 import json, sys
 d = json.load(open(sys.argv[1]))
