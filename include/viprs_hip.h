@@ -135,7 +135,7 @@ int viprs_plan_set_math_mode(viprs_plan* plan, int math_mode);
  * :1079-1086) and each of those fits stops at its own iteration (VIPRS.py:1046-1094); with the chromosomes' blocks in ONE
  * plan (viprs_state_set_groups below) a converged chromosome's blocks leave the sweep this way -- its state stays as its
  * last E-step left it.  Host-side list surgery over a few thousand descriptors; LD and per-SNP arrays do not move.
- * Not supported by the batched grid kernel (VIPRS_EUNSUPPORTED from viprs_state_e_step on a grid state). */
+ * Every kernel family sweeps the active subset, the batched grid kernel included (it rebuilds its teams from the new list). */
 int viprs_plan_set_active_blocks(viprs_plan* plan, const uint8_t* active, int64_t n_blocks);
 
 /* ---- one-shot calls on host buffers: the drop-ins for the Cython entry points ------------ */
@@ -262,7 +262,7 @@ int viprs_state_reset_column(viprs_state* state, int g, double pi);
  * A chromosome-sized fit cannot fill the device (its sweep is bound by the chain of its largest LD block), 22 of them in
  * one plan cost one genome-wide sweep.  A GROUP is a contiguous SNP range made of whole LD blocks:
  *   viprs_state_set_groups        group g = SNPs [group_start[g], group_start[g+1]); n_groups + 1 entries covering 0 .. m;
- *                                 n_groups = 0 removes the groups.  Spike-and-slab and mixture (K <= 8) states.
+ *                                 n_groups = 0 removes the groups.  Spike-and-slab, mixture (K <= 8) and grid states.
  *   viprs_state_prep_groups       viprs_state_prep with per-group scalars: n rows of 6 doubles
  *                                 (group, logit_pi, log_tau_beta, sigma_epsilon, tau_beta, one_plus_lambda); only the listed
  *                                 groups' SNPs are rewritten (a converged group keeps the inputs of its last E-step).
@@ -286,6 +286,27 @@ int viprs_state_sums_groups_end(viprs_state* state, double* out);
 int viprs_state_prep_mixture_groups(viprs_state* state, int n, const double* params);
 int viprs_state_sums_mixture_groups_begin(viprs_state* state, int n, const double* rows);
 int viprs_state_sums_mixture_groups_end(viprs_state* state, double* out);
+/* The same for a GRID state (one VIPRSGrid per chromosome, every grid point fitted from the standard start): one set of
+ * hyper-parameters per (group, column) pair -- a group is a chromosome, a column a grid point.
+ *   viprs_state_prep_grid_groups          viprs_state_prep_columns per pair: n rows of 7 doubles (group, column, logit_pi,
+ *                                         log_tau_beta, sigma_epsilon, tau_beta, one_plus_lambda); only the listed pairs'
+ *                                         SNPs x column are rewritten; each pair's scalars are kept for its sums (a grid
+ *                                         state keeps no var_tau, see viprs_state_prep_column)
+ *   viprs_state_sums_grid_groups_begin    n rows of 3 doubles (group, column, one_plus_lambda): the VIPRS_N_SUMS sums per pair
+ *                                         in one launch, [0] the plain sum of gamma
+ *   viprs_state_sums_grid_groups_end      n rows of VIPRS_N_SUMS doubles in the order of the rows given to `begin`
+ *   viprs_state_set_group_columns         n_groups x width row-major mask (non-zero = on); n_groups = 0 clears it.  Under a
+ *                                         mask, viprs_state_e_step sweeps column g of group c only if g is in
+ *                                         active_model_idx AND active[c][g] is set; every other pair keeps every bit of its
+ *                                         var_gamma / var_mu / eta / q / eta_diff.  fp32 states on dense blocks (the batched
+ *                                         matrix-core kernel and the panel kernel); float64 states and ragged / banded blocks
+ *                                         under a mask: VIPRS_EUNSUPPORTED.
+ * A pair's inputs, sweep and sums are bit-identical to those of column `column` of a grid state whose plan holds only that
+ * group's blocks (swept with that group's active list).  viprs_state_set_groups clears the pairs' scalars and the mask. */
+int viprs_state_prep_grid_groups(viprs_state* state, int n, const double* params);
+int viprs_state_sums_grid_groups_begin(viprs_state* state, int n, const double* rows);
+int viprs_state_sums_grid_groups_end(viprs_state* state, double* out);
+int viprs_state_set_group_columns(viprs_state* state, int n_groups, int width, const uint8_t* active);
 
 /* ---- multi-GPU: RCCL over xGMI for the scalar reductions of the EM iteration -------------------------
  * One process per GPU; LD blocks are sharded over the ranks (independent units: within one E-step call

@@ -216,6 +216,11 @@ int run_generic_model(viprs_state* S, double dq, int model, const int32_t* d_act
         EStepArgs<float> A = make_args<float>(S, dq);
         A.active = d_active;
         A.n_active = n_active;
+        if (model == kGenGrid && !S->group_cols_h.empty()) {     // (group_mask_prepare: dense blocks only)
+            A.blk_group = S->d_blk_group.p;
+            A.group_cols = S->d_group_cols.p;
+        }
+        const int64_t lists_per_chunk = (int64_t)S->n_groups * kGroupListStride;
         const bool panel_ok = !P->dense_h.empty() && (model == kGenGrid || S->width <= kPanelWideMaxK);
         if (panel_ok && model == kGenMixture) {
             rc = launch_panel_u(P, A, S->width <= kPanelMaxK ? kPanelMixture : kPanelMixtureWide);
@@ -225,6 +230,7 @@ int run_generic_model(viprs_state* S, double dq, int model, const int32_t* d_act
                 EStepArgs<float> Ac = A;
                 Ac.active = d_active + off;
                 Ac.n_active = std::min(kGridModels, n_active - off);
+                if (A.group_cols) Ac.group_lists = S->d_group_lists.p + (off / kGridModels) * lists_per_chunk;
                 if (off > 0) rc = sweep_prologue(P, 1);
                 if (rc == VIPRS_OK) rc = launch_grid_mfma_u(P, Ac);
             }
@@ -255,6 +261,47 @@ int run_generic_model(viprs_state* S, double dq, int model, const int32_t* d_act
     return VIPRS_OK;
 }
 
+// A grid state with SNP groups under a (group, column) mask (viprs_state_set_group_columns): the batched matrix-core kernel
+// and the panel kernel's (block, model) items take the mask; the kernels of the other paths have none and refuse.  The
+// group of every block of the dense list, indexed as the list is, is rebuilt whenever the list changes.
+int group_mask_prepare(viprs_state* S, const int32_t* active, int n_active) {
+    viprs_plan* P = S->plan;
+    if (S->float_dtype != VIPRS_F32)
+        return fail(VIPRS_EUNSUPPORTED, "grid state with a (group, column) mask: float64 states are not supported");
+    if (!P->ragged_h.empty())
+        return fail(VIPRS_EUNSUPPORTED, "grid state with a (group, column) mask: ragged / banded LD blocks are not supported "
+                                        "(the generic and band kernels take no mask)");
+    // the matrix-core kernel's per-group lists of this call: launch k covers active[32 k .. 32 k + 31]; a group's list is
+    // that chunk's columns whose mask byte is set, in order, padded with the last of them (or with the chunk's first column
+    // when there is none: the block is skipped)
+    const int n_chunks = (n_active + kGridModels - 1) / kGridModels;
+    std::vector<int32_t> lists((size_t)n_chunks * S->n_groups * kGroupListStride, 0);
+    for (int k = 0; k < n_chunks; ++k) {
+        const int lo = k * kGridModels, hi = std::min(n_active, lo + kGridModels);
+        for (int g = 0; g < S->n_groups; ++g) {
+            int32_t* l = lists.data() + ((size_t)k * S->n_groups + g) * kGroupListStride;
+            int cnt = 0;
+            for (int i = lo; i < hi; ++i)
+                if (S->group_cols_h[(size_t)g * S->width + active[i]]) l[1 + cnt++] = active[i];
+            l[0] = cnt;
+            for (int t = cnt; t < kGridModels; ++t) l[1 + t] = cnt > 0 ? l[cnt] : active[lo];
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(P->stream));              // (a sweep in flight may read the old lists / map)
+    if (S->d_group_lists.n < lists.size()) HIP_TRY(S->d_group_lists.alloc(lists.size()));
+    HIP_TRY(hipMemcpy(S->d_group_lists.p, lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (S->blk_group_gen != P->dense_gen || S->d_blk_group.n < P->dense_h.size()) {
+        std::vector<int32_t> map(std::max<size_t>(1, P->dense_h.size()), 0);
+        for (size_t k = 0; k < P->dense_h.size(); ++k)     // (an empty group shares its start with the next one: `upper_bound`)
+            map[k] = (int32_t)(std::upper_bound(S->group_start.begin(), S->group_start.end(), (int64_t)P->dense_h[k].start) -
+                               S->group_start.begin()) - 1;
+        HIP_TRY(S->d_blk_group.alloc(map.size()));
+        HIP_TRY(hipMemcpy(S->d_blk_group.p, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        S->blk_group_gen = P->dense_gen;
+    }
+    return VIPRS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -277,6 +324,10 @@ int viprs_state_e_step(viprs_state* S, double dq_scale, const int32_t* active, i
                 if (active[i] < 0 || active[i] >= S->width) return fail(VIPRS_EINVAL, "active_model_idx out of range");
             if (n_active == 0) return VIPRS_OK;
             HIP_TRY(hipSetDevice(S->plan->device));
+            if (!S->group_cols_h.empty()) {
+                rc = group_mask_prepare(S, active, n_active);
+                if (rc != VIPRS_OK) return rc;
+            }
             if (S->d_active.n < (size_t)n_active) HIP_TRY(S->d_active.alloc((size_t)std::max(n_active, S->width)));
             HIP_TRY(hipMemcpyAsync(S->d_active.p, active, sizeof(int32_t) * (size_t)n_active, hipMemcpyHostToDevice,
                                    S->plan->stream));

@@ -678,6 +678,7 @@ int viprs_plan_set_active_blocks(viprs_plan* P, const uint8_t* active, int64_t n
     // schedules derived from the lists: rebuilt on the next launch that needs them
     P->team_split = viprs_plan::TeamSplit();
     P->grid_teams_built = false;
+    P->dense_gen++;
     HIP_TRY(P->d_rowlist_dense.alloc(0));
     HIP_TRY(P->d_rowlist_ragged.alloc(0));
     return VIPRS_OK;

@@ -387,6 +387,73 @@ __global__ void sums_final_generic_groups_kernel(const double* __restrict__ part
     if (lane == 0) out[(int64_t)blockIdx.y * n_sums + k] = a;
 }
 
+// ---- SNP groups of a GRID state: one set of hyper-parameters per (group, column) pair (one VIPRSGrid per chromosome) ----
+// workgroups of the reduction of one column over `count` SNPs: what viprs_state_sums_columns uses for a plan of that size
+__host__ __device__ inline int grid_sums_blocks(int64_t count) {
+    const int64_t nb = (count + kSumsBlock - 1) / kSumsBlock;
+    return (int)(nb < 256 ? nb : 256);
+}
+
+// prep_columns_kernel for (group, column) pairs: blockIdx.y picks a row of `params` (group, column, logit_pi,
+// log_tau_beta, sigma_eps, tau_beta, one_plus_lambda); only the group's SNPs of that column are written
+template <typename T>
+__global__ void prep_grid_groups_kernel(const double* __restrict__ n, int64_t m, const int64_t* __restrict__ gstart,
+                                        const double* __restrict__ params, T* __restrict__ mu_mult, T* __restrict__ u_logs,
+                                        T* __restrict__ shvt) {
+    const double* __restrict__ p = params + 7 * (int64_t)blockIdx.y;
+    const int g = (int)p[0];
+    const int64_t off = (int64_t)p[1] * m;
+    const double logit_pi = p[2], log_tau_beta = p[3], sigma_eps = p[4], tau_beta = p[5], one_plus_lambda = p[6];
+    const int64_t end = gstart[g + 1];
+    for (int64_t i = gstart[g] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (int64_t)gridDim.x * blockDim.x) {
+        const double vt = n[i] * one_plus_lambda / sigma_eps + tau_beta;
+        mu_mult[off + i] = (T)(n[i] / (vt * sigma_eps));
+        u_logs[off + i] = (T)(logit_pi + 0.5 * (log_tau_beta - log(vt)));
+        shvt[off + i] = (T)(0.5 * vt);                                    // e_step_grid takes var_tau / 2 (e_step.hpp:616)
+    }
+}
+
+// the sums of (group, column) pairs: blockIdx.y picks a row (group, column, one_plus_lambda, and the scalars the pair's last
+// prep built var_tau from: one_plus_lambda, sigma_eps, tau_beta); the pair is reduced by grid_sums_blocks(group's SNPs)
+// workgroups in the element order of sums_kernel over a plan that holds only the group
+template <typename T>
+__global__ __launch_bounds__(kSumsBlock) void sums_grid_groups_kernel(int64_t m, const int64_t* __restrict__ gstart,
+                                                                      const double* __restrict__ rows, const T* __restrict__ gam,
+                                                                      const T* __restrict__ mu, const T* __restrict__ eta,
+                                                                      const T* __restrict__ q, const T* __restrict__ ed,
+                                                                      const T* __restrict__ beta, const double* __restrict__ n_snp,
+                                                                      double* __restrict__ partials) {
+    const double* __restrict__ r = rows + 6 * (int64_t)blockIdx.y;
+    const int g = (int)r[0];
+    const int64_t off = (int64_t)r[1] * m;
+    const int64_t i0 = gstart[g], i1 = gstart[g + 1];
+    const int nb = grid_sums_blocks(i1 - i0);
+    if ((int)blockIdx.x >= nb) return;
+    sums_body<T>(i0, i1, nb, (int)blockIdx.x, gam + off, mu + off, eta + off, q + off, ed + off, beta, nullptr, r[2], nullptr,
+                 partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kNSums, n_snp, r[3], r[4], r[5]);
+}
+
+// sums_final_kernel per pair: workgroup y adds the grid_sums_blocks(group's SNPs) partials of row y (`stride` slots per row)
+__global__ void sums_final_grid_groups_kernel(const double* __restrict__ partials, int stride, const int64_t* __restrict__ gstart,
+                                              const double* __restrict__ rows, double* __restrict__ out) {
+    const int g = (int)rows[6 * blockIdx.x];
+    const int n_blocks = grid_sums_blocks(gstart[g + 1] - gstart[g]);
+    partials += (int64_t)blockIdx.x * stride * kNSums;
+    out += (int64_t)blockIdx.x * kNSums;
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (k >= kNSums) return;
+    const bool is_max = (k == kNSums - 1);
+    double a = 0.0;
+    for (int b = lane; b < n_blocks; b += 64) {
+        const double v = partials[(int64_t)b * kNSums + k];
+        a = is_max ? fmax(a, v) : a + v;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(a, off, 64);
+        a = is_max ? fmax(a, o) : a + o;
+    }
+    if (lane == 0) out[k] = a;
+}
 
 }  // namespace
 
@@ -974,6 +1041,7 @@ int viprs_state_reset_column(viprs_state* S, int g, double pi) {
 
 // doubles per row of the groups' prep parameters (viprs_state_prep_groups / viprs_state_prep_mixture_groups)
 static size_t group_prep_width(const viprs_state* S) {
+    if (S->model_kind == VIPRS_MODEL_GRID) return 7;
     return S->model_kind == VIPRS_MODEL_MIXTURE ? (size_t)4 + 3 * (size_t)S->width : 6;
 }
 
@@ -981,12 +1049,18 @@ static size_t group_prep_width(const viprs_state* S) {
 // model per chromosome unless --genomewide; the chromosomes' LD blocks are independent, so their E-steps share one sweep)
 int viprs_state_set_groups(viprs_state* S, int n_groups, const int64_t* group_start) {
     if (!S) return fail(VIPRS_EINVAL, "null state");
-    if (S->model_kind != VIPRS_MODEL_SPIKE_SLAB && S->model_kind != VIPRS_MODEL_MIXTURE)
-        return fail(VIPRS_EUNSUPPORTED, "SNP groups: spike-and-slab and mixture states only");
     if (S->model_kind == VIPRS_MODEL_MIXTURE && S->width > kMixResidentK)
         return fail(VIPRS_EUNSUPPORTED, "device-resident mixture iteration: K <= 8");
     viprs_plan* P = S->plan;
+    const bool grid = S->model_kind == VIPRS_MODEL_GRID;
+    // (a grid state's pair scalars and mask belong to the groups they were given for: dropped once the new list is valid)
+    auto drop_pairs = [&]() {
+        S->pair_prep.clear();
+        S->group_cols_h.clear();
+        S->blk_group_gen = ~0ull;
+    };
     if (n_groups == 0) {                         // back to one set of hyper-parameters
+        drop_pairs();
         S->n_groups = 0;
         S->group_start.clear();
         return VIPRS_OK;
@@ -1002,17 +1076,22 @@ int viprs_state_set_groups(viprs_state* S, int n_groups, const int64_t* group_st
     }
     HIP_TRY(hipSetDevice(P->device));
     HIP_TRY(hipStreamSynchronize(P->stream));
+    drop_pairs();
     S->n_groups = n_groups;
     S->group_start.assign(group_start, group_start + n_groups + 1);
     S->group_max_nb = 1;
-    for (int g = 0; g < n_groups; ++g) S->group_max_nb = std::max(S->group_max_nb, sums_blocks(group_start[g + 1] - group_start[g]));
+    for (int g = 0; g < n_groups; ++g)
+        S->group_max_nb = std::max(S->group_max_nb, grid ? grid_sums_blocks(group_start[g + 1] - group_start[g])
+                                                          : sums_blocks(group_start[g + 1] - group_start[g]));
     HIP_TRY(S->d_group_start.alloc((size_t)n_groups + 1));
     HIP_TRY(hipMemcpy(S->d_group_start.p, group_start, sizeof(int64_t) * ((size_t)n_groups + 1), hipMemcpyHostToDevice));
-    const size_t pw = group_prep_width(S);
-    HIP_TRY(S->d_group_prep.alloc(pw * n_groups));
-    HIP_TRY(S->d_group_sumrows.alloc((size_t)2 * n_groups));
+    // rows per launch: one per group, or (grid) one per (group, column) pair
+    const size_t pw = group_prep_width(S), sw = grid ? 6 : 2, rows = (size_t)n_groups * (grid ? S->width : 1);
+    HIP_TRY(S->d_group_prep.alloc(pw * rows));
+    HIP_TRY(S->d_group_sumrows.alloc(sw * rows));
     if (S->h_gparams) { HIP_TRY(hipHostFree(S->h_gparams)); S->h_gparams = nullptr; }
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_gparams), (pw + 2) * n_groups * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_gparams), (pw + sw) * rows * sizeof(double), hipHostMallocDefault));
+    if (grid) S->pair_prep.assign((size_t)3 * rows, NAN);
     return VIPRS_OK;
 }
 
@@ -1232,6 +1311,155 @@ int viprs_state_sums_mixture_groups_end(viprs_state* S, double* out) {
     int32_t e = 0;
     memcpy(&e, S->h_sums + total, sizeof(e));
     return e != 0 ? check_device_error(P) : VIPRS_OK;
+}
+
+}  // extern "C"
+
+// ---- SNP groups of a grid state: (group, column) pairs ------------------------------------------------------------------
+static int pair_rows_check(const viprs_state* S, int n, const double* rows, int width) {
+    if (!S || (n > 0 && !rows)) return fail(VIPRS_EINVAL, "null argument");
+    if (S->model_kind != VIPRS_MODEL_GRID) return fail(VIPRS_EINVAL, "not a grid state");
+    if (S->n_groups == 0) return fail(VIPRS_EINVAL, "viprs_state_set_groups has not been called");
+    if (S->pair_prep.size() != (size_t)3 * S->n_groups * S->width)
+        return fail(VIPRS_EINVAL, "the grid state's groups are not set up (viprs_state_set_groups)");
+    if (n < 0 || (int64_t)n > (int64_t)S->n_groups * S->width) return fail(VIPRS_EINVAL, "bad row count");
+    for (int i = 0; i < n; ++i) {
+        const double g = rows[(size_t)width * i], c = rows[(size_t)width * i + 1];
+        if (g < 0 || g >= S->n_groups || g != floor(g)) return fail(VIPRS_EINVAL, "group index out of range");
+        if (c < 0 || c >= S->width || c != floor(c)) return fail(VIPRS_EINVAL, "model index out of range");
+    }
+    return VIPRS_OK;
+}
+
+static size_t pair_index(const viprs_state* S, double g, double c) { return (size_t)g * (size_t)S->width + (size_t)c; }
+
+extern "C" {
+
+int viprs_state_prep_grid_groups(viprs_state* S, int n, const double* params) {
+    int rc = pair_rows_check(S, n, params, 7);
+    if (rc != VIPRS_OK) return rc;
+    viprs_plan* P = S->plan;
+    if (P->m == 0 || n == 0) return VIPRS_OK;
+    if (!S->d_n.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp has not been called");
+    HIP_TRY(hipSetDevice(P->device));
+    for (int i = 0; i < n; ++i) {                 // what the pair's sums form var_tau from
+        const double* p = params + (size_t)7 * i;
+        const size_t k = 3 * pair_index(S, p[0], p[1]);
+        S->pair_prep[k] = p[6];
+        S->pair_prep[k + 1] = p[4];
+        S->pair_prep[k + 2] = p[5];
+    }
+    if (!S->ev_prep) HIP_TRY(hipEventCreateWithFlags(&S->ev_prep, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(S->ev_prep));            // the previous launch has read its parameters
+    memcpy(S->h_gparams, params, (size_t)7 * n * sizeof(double));
+    HIP_TRY(hipMemcpyAsync(S->d_group_prep.p, S->h_gparams, (size_t)7 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
+    int64_t longest = 0;
+    for (int i = 0; i < n; ++i) {
+        const int g = (int)params[(size_t)7 * i];
+        longest = std::max(longest, S->group_start[(size_t)g + 1] - S->group_start[(size_t)g]);
+    }
+    const dim3 grid((unsigned)std::max<int64_t>(1, (longest + 255) / 256), (unsigned)n);
+    if (S->float_dtype == VIPRS_F32)
+        prep_grid_groups_kernel<float><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, S->d_group_start.p, S->d_group_prep.p,
+                                                                    (float*)S->f[VIPRS_FIELD_MU_MULT].p, (float*)S->f[VIPRS_FIELD_U_LOGS].p,
+                                                                    (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p);
+    else
+        prep_grid_groups_kernel<double><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, S->d_group_start.p, S->d_group_prep.p,
+                                                                     (double*)S->f[VIPRS_FIELD_MU_MULT].p, (double*)S->f[VIPRS_FIELD_U_LOGS].p,
+                                                                     (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S->ev_prep, P->stream));
+    return VIPRS_OK;
+}
+
+}  // extern "C"
+
+template <typename T>
+static int sums_grid_groups_enqueue(viprs_state* S, int n) {
+    viprs_plan* P = S->plan;
+    const int nb = S->group_max_nb;
+    const size_t need = (size_t)nb * kNSums * n;
+    if (S->d_partials.n < need) HIP_TRY(S->d_partials.alloc(need));
+    if (S->d_sums.n < (size_t)kNSums * n) HIP_TRY(S->d_sums.alloc((size_t)kNSums * n));
+    const size_t hcap = (size_t)kNSums * n + 1;
+    if (S->h_sums_cap < hcap) {
+        if (S->h_sums) HIP_TRY(hipHostFree(S->h_sums));
+        S->h_sums = nullptr;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), hcap * sizeof(double), hipHostMallocDefault));
+        S->h_sums_cap = hcap;
+    }
+    sums_grid_groups_kernel<T><<<dim3(nb, n), kSumsBlock, 0, P->stream>>>(
+        P->m, S->d_group_start.p, S->d_group_sumrows.p, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const T*)S->f[VIPRS_FIELD_VAR_MU].p,
+        (const T*)S->f[VIPRS_FIELD_ETA].p, (const T*)S->f[VIPRS_FIELD_Q].p, (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p,
+        (const T*)S->f[VIPRS_FIELD_STD_BETA].p, S->d_n.p, S->d_partials.p);
+    HIP_TRY(hipGetLastError());
+    sums_final_grid_groups_kernel<<<n, 64 * kNSums, 0, P->stream>>>(S->d_partials.p, nb, S->d_group_start.p, S->d_group_sumrows.p,
+                                                                     S->d_sums.p);
+    HIP_TRY(hipGetLastError());
+    if (S->comm) {
+        const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, kNSums * n, kNSums, P->stream);
+        if (rc != VIPRS_OK) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, (size_t)kNSums * n * sizeof(double), hipMemcpyDeviceToHost, P->stream));
+    HIP_TRY(hipMemcpyAsync(S->h_sums + (size_t)kNSums * n, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
+    S->sums_cols = n;
+    S->sums_pending = true;
+    return VIPRS_OK;
+}
+
+extern "C" {
+
+int viprs_state_sums_grid_groups_begin(viprs_state* S, int n, const double* rows) {
+    int rc = pair_rows_check(S, n, rows, 3);
+    if (rc != VIPRS_OK) return rc;
+    viprs_plan* P = S->plan;
+    S->sums_cols = n;
+    if (P->m == 0 && n > 0 && S->comm) return sums_enqueue_empty(S, kNSums * n, kNSums);
+    if (P->m == 0 || n == 0) { S->sums_pending = false; S->sums_empty = true; return VIPRS_OK; }
+    S->sums_empty = false;
+    for (int i = 0; i < n; ++i)
+        if (std::isnan(S->pair_prep[3 * pair_index(S, rows[(size_t)3 * i], rows[(size_t)3 * i + 1])]))
+            return fail(VIPRS_EINVAL, "viprs_state_prep_grid_groups has not been called for this (group, column) pair");
+    HIP_TRY(hipSetDevice(P->device));
+    // device rows (group, column, one_plus_lambda | the pair's last prep); own half of the pinned staging: the previous
+    // reduction that read it has been collected
+    double* h = S->h_gparams + (size_t)7 * S->n_groups * S->width;
+    for (int i = 0; i < n; ++i) {
+        const size_t k = 3 * pair_index(S, rows[(size_t)3 * i], rows[(size_t)3 * i + 1]);
+        h[6 * i] = rows[(size_t)3 * i];
+        h[6 * i + 1] = rows[(size_t)3 * i + 1];
+        h[6 * i + 2] = rows[(size_t)3 * i + 2];
+        h[6 * i + 3] = S->pair_prep[k];
+        h[6 * i + 4] = S->pair_prep[k + 1];
+        h[6 * i + 5] = S->pair_prep[k + 2];
+    }
+    HIP_TRY(hipMemcpyAsync(S->d_group_sumrows.p, h, (size_t)6 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
+    return S->float_dtype == VIPRS_F32 ? sums_grid_groups_enqueue<float>(S, n) : sums_grid_groups_enqueue<double>(S, n);
+}
+
+int viprs_state_sums_grid_groups_end(viprs_state* S, double* out) {
+    if (!S || !out) return fail(VIPRS_EINVAL, "null argument");
+    if (S->model_kind != VIPRS_MODEL_GRID) return fail(VIPRS_EINVAL, "not a grid state");
+    if (S->n_groups == 0) return fail(VIPRS_EINVAL, "viprs_state_set_groups has not been called");
+    return viprs_state_sums_columns_end(S, out);          // same landing buffer and bookkeeping: sums_cols rows of VIPRS_N_SUMS
+}
+
+int viprs_state_set_group_columns(viprs_state* S, int n_groups, int width, const uint8_t* active) {
+    if (!S) return fail(VIPRS_EINVAL, "null state");
+    if (S->model_kind != VIPRS_MODEL_GRID) return fail(VIPRS_EINVAL, "not a grid state");
+    if (n_groups == 0) { S->group_cols_h.clear(); return VIPRS_OK; }
+    if (!active) return fail(VIPRS_EINVAL, "null argument");
+    if (S->n_groups == 0) return fail(VIPRS_EINVAL, "viprs_state_set_groups has not been called");
+    if (n_groups != S->n_groups || width != S->width) return fail(VIPRS_EINVAL, "the mask must be n_groups x width of the state");
+    viprs_plan* P = S->plan;
+    HIP_TRY(hipSetDevice(P->device));
+    const size_t n = (size_t)n_groups * (size_t)width;
+    HIP_TRY(hipStreamSynchronize(P->stream));              // (a sweep in flight reads the old mask)
+    if (S->d_group_cols.n != n) HIP_TRY(S->d_group_cols.alloc(n));
+    S->group_cols_h.assign(active, active + n);
+    for (uint8_t& v : S->group_cols_h) v = v ? 1 : 0;
+    HIP_TRY(hipMemcpy(S->d_group_cols.p, S->group_cols_h.data(), n, hipMemcpyHostToDevice));
+    return VIPRS_OK;
 }
 
 }  // extern "C"

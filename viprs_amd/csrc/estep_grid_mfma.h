@@ -905,10 +905,30 @@ struct GridTeams {
     uint32_t tag_base = 0;
 };
 
+// GROUPED kernel: the models of block `blk` -- its group's list of this launch (host-built: the chunk of active columns
+// the group's mask leaves on, compacted, padded with the last of them) -- into s_act; the count is returned, uniform.  A
+// plain load per block: nothing of the mask stays live across the sweep.  Called by every thread after a barrier that all
+// readers of the previous list have passed.
+__device__ __forceinline__ int grid_group_models(const int32_t* __restrict__ blk_group, const int32_t* __restrict__ lists,
+                                                 int* s_act, int blk, int tid) {
+    const int32_t* __restrict__ l = lists + (int64_t)__builtin_amdgcn_readfirstlane(blk_group[__builtin_amdgcn_readfirstlane(blk)]) *
+                                                kGroupListStride;
+    if (tid < kGridModels) s_act[tid] = l[1 + tid];
+    const int cnt = __builtin_amdgcn_readfirstlane(l[0]);
+    __syncthreads();
+    return cnt;
+}
+
 // Every block of a launch takes the resident form or a team (the host deals the blocks beyond kGridResMaxCols to teams, in
 // several launches when they do not fit the chip at once: launch_grid.inc).  SYM: the symmetric form; otherwise the
 // upper-triangular arithmetic over the MIRRORED storage (abi_plan.hip: mirror_lower_kernel).
-template <typename U, bool SYM, bool EXACT>
+// GROUPED: a grid state with SNP groups under a (group, column) mask (viprs_state_set_group_columns).  The models of a block
+// are then the launch's chunk of active columns that the mask of the block's group leaves on, compacted into the first
+// slots of s_act (padded as the ungrouped kernel pads; one host-built list per group and launch) -- a per-block model
+// count; a block without any is skipped by all waves (every member of a team reads the same list).  A column's arithmetic does not depend on its slot, so a masked
+// sweep is bit for bit the ungrouped sweep of each group with its own active list.  (A separate instantiation: the
+// ungrouped kernel keeps its registers and its timing.)
+template <typename U, bool SYM, bool EXACT, bool GROUPED = false>
 __global__ __launch_bounds__(64 * kGridWaves) void estep_grid_mfma_kernel(EStepArgs<float> A, GridTeams teams) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* io = smem;                                   // [2][4][32][65]: mm, ulog, hvt, eta -> mu, gamma, d, eta'
@@ -935,7 +955,12 @@ __global__ __launch_bounds__(64 * kGridWaves) void estep_grid_mfma_kernel(EStepA
         tm.size = teams.size[blockIdx.x];
         tm.gran = teams.gran + teams.goff[tb];
         tm.tag_base = teams.tag_base;
-        grid_block_resident<U, SYM, EXACT>(A, io, la, dg, cy, qx, s_act, A.blocks[tb], wave, lane, n_models, dq, tab, tm);
+        if constexpr (GROUPED) {
+            const int nm = grid_group_models(A.blk_group, A.group_lists, s_act, tb, tid);
+            if (nm > 0) grid_block_resident<U, SYM, EXACT>(A, io, la, dg, cy, qx, s_act, A.blocks[tb], wave, lane, nm, dq, tab, tm);
+        } else {
+            grid_block_resident<U, SYM, EXACT>(A, io, la, dg, cy, qx, s_act, A.blocks[tb], wave, lane, n_models, dq, tab, tm);
+        }
         __syncthreads();
     }
     for (;;) {
@@ -953,6 +978,11 @@ __global__ __launch_bounds__(64 * kGridWaves) void estep_grid_mfma_kernel(EStepA
             continue;
         }
         // q of the whole block fits the updater waves' accumulator registers
+        if constexpr (GROUPED) {
+            const int nm = grid_group_models(A.blk_group, A.group_lists, s_act, blk, tid);
+            if (nm > 0) grid_block_resident<U, SYM, EXACT>(A, io, la, dg, cy, qx, s_act, bd, wave, lane, nm, dq, tab);
+            continue;
+        }
         grid_block_resident<U, SYM, EXACT>(A, io, la, dg, cy, qx, s_act, bd, wave, lane, n_models, dq, tab);
     }
 }

@@ -377,6 +377,9 @@ struct GridColumnModel {
     }
 };
 
+template <typename MODEL> struct IsGridColumn : std::false_type {};
+template <bool EXACT> struct IsGridColumn<GridColumnModel<EXACT>> : std::true_type {};
+
 // exp(x), x <= 0, of the softmax (e_step.hpp:231-240): glibc's expf bit for bit, or v_exp_f32 (math_mode = fast)
 template <bool EXACT, int LOOKUP>
 __device__ __forceinline__ float softmax_exp(float x, const ExpTab& tab, int sel = 0) {
@@ -596,6 +599,14 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
         // models of one block are adjacent in the queue, so the workgroups that stream the same LD
         // rows for different models run at about the same time and share them through L2 / MALL
         const int blk = item / n_models, model_slot = item - blk * n_models;
+        if constexpr (IsGridColumn<MODEL>::value) {
+            // a grid state under a (group, column) mask: an item whose column is off for the block's group is skipped by
+            // the whole workgroup (a team's members all skip it) -- no store, no q contribution
+            if (A0.group_cols) {
+                const int on = A0.group_cols[(int64_t)A0.blk_group[blk] * A0.width + A0.active[model_slot]];
+                if (__builtin_amdgcn_readfirstlane(on) == 0) continue;
+            }
+        }
         const EStepArgs<float> A = select_model(A0, model_slot);
 
         const BlockDesc bd = A.blocks[blk];

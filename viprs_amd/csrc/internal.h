@@ -106,6 +106,7 @@ struct viprs_plan {
     int max_dense_all = 0, max_ragged_all = 0;
     viprs::DevBuf<viprs::BlockDesc> d_dense_all;   // what ensure_upper_storage converts (every block, active or not)
     bool filtered = false;
+    uint64_t dense_gen = 0;                        // changes of the dense list (viprs_plan_set_active_blocks): maps indexed like it follow
     int64_t m_active = 0;                          // SNPs of the blocks a sweep visits
     viprs::DevBuf<unsigned long long> d_granules;  // team hand-off granules (one row of 64 per panel of a team block)
     int64_t n_granule_rows = 0;
@@ -175,6 +176,13 @@ struct viprs_state {
     viprs::DevBuf<int64_t> d_group_start;
     viprs::DevBuf<double> d_group_prep, d_group_sumrows;   // per-launch parameter rows (6, mixture: 4 + 3 K / 2 doubles per listed group)
     double* h_gparams = nullptr;                   // pinned staging of both
+    // grid state with groups: one set of hyper-parameters per (group, column) pair
+    std::vector<double> pair_prep;                 // (one_plus_lambda, sigma_eps, tau_beta) of every pair's last prep (3 x n_groups x width; NaN: none yet)
+    std::vector<uint8_t> group_cols_h;             // viprs_state_set_group_columns: n_groups x width mask (empty: none)
+    viprs::DevBuf<uint8_t> d_group_cols;
+    viprs::DevBuf<int32_t> d_blk_group;            // group of every block of the plan's dense list (indexed as d_dense)
+    uint64_t blk_group_gen = ~0ull;                // the plan's dense_gen d_blk_group was built for
+    viprs::DevBuf<int32_t> d_group_lists;          // per launch of 32 active columns and group: its columns under the mask (kGroupListStride ints)
     size_t h_sums_cap = 0;
     double* h_sums = nullptr;               // pinned landing buffer of the device sums
     bool sums_pending = false, sums_empty = false;

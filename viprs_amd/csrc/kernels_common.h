@@ -187,7 +187,16 @@ struct EStepArgs {
     int64_t m;            // SNPs in the plan (column stride of grid matrices)
     const int32_t* active; // grid: active model indices
     int32_t n_active;
+    // grid state with SNP groups under a (group, column) mask (viprs_state_set_group_columns), otherwise null: the group of
+    // every block of `blocks` (indexed as `blocks` is) and the n_groups x width mask; column g of a block's group is swept
+    // only if g is active AND its mask byte is set.  `group_lists` (batched matrix-core kernel): per group, the launch's
+    // chunk of active columns that the mask leaves on -- kGroupListStride ints: count, then the columns compacted and
+    // padded with the last of them (the host builds them per launch, abi_estep.hip)
+    const int32_t* blk_group;
+    const uint8_t* group_cols;
+    const int32_t* group_lists;
 };
+constexpr int kGroupListStride = 1 + kGridModels;  // count + the columns of one launch
 
 // Grid launches run (block, model) work items: the same kernels, with every (m, G) column-major array
 // offset to the model's column.  n_active == 0 means a plain (m,) state (one "model", no offset).

@@ -16,9 +16,14 @@ int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A) {
     const size_t shmem = (size_t)kGridLdsFloats * sizeof(float);
     const bool exact = P->math_mode == VIPRS_MATH_EXACT;      // fast: the chain's sigmoid on v_exp_f32 / v_rcp_f32
     // upper-triangular form: the sweep runs over the MIRRORED storage and carries the second pass itself (grid_block_resident)
-    const void* kfn = P->low_memory
-        ? (exact ? (const void*)estep_grid_mfma_kernel<U, false, true> : (const void*)estep_grid_mfma_kernel<U, false, false>)
-        : (exact ? (const void*)estep_grid_mfma_kernel<U, true, true> : (const void*)estep_grid_mfma_kernel<U, true, false>);
+    // (grouped: a grid state with a (group, column) mask -- per-block model lists, estep_grid_mfma.h)
+    const void* kfn = A.group_lists
+        ? (P->low_memory
+           ? (exact ? (const void*)estep_grid_mfma_kernel<U, false, true, true> : (const void*)estep_grid_mfma_kernel<U, false, false, true>)
+           : (exact ? (const void*)estep_grid_mfma_kernel<U, true, true, true> : (const void*)estep_grid_mfma_kernel<U, true, false, true>))
+        : (P->low_memory
+           ? (exact ? (const void*)estep_grid_mfma_kernel<U, false, true> : (const void*)estep_grid_mfma_kernel<U, false, false>)
+           : (exact ? (const void*)estep_grid_mfma_kernel<U, true, true> : (const void*)estep_grid_mfma_kernel<U, true, false>));
     P->math_used |= exact ? 1 : 2;
     HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     int per_cu = 0;

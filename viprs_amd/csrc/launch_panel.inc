@@ -67,6 +67,7 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
         const int begin = P->class_begin[c], end = P->class_begin[c + 1];
         C.blocks = P->d_dense.p + begin;
         C.n_blocks = end - begin;
+        if (A.blk_group) C.blk_group = A.blk_group + begin;       // (indexed as `blocks`)
         C.counter = c < 2 ? P->d_counters.p + 4 + c : P->d_counters.p + 16;
         // arrival counters: the items of class 0, then those of class 1
         C.arrive = P->d_arrive.p + (c == 1 ? (size_t)(P->class_begin[1] - P->class_begin[0]) * (size_t)n_models : 0);

@@ -24,6 +24,7 @@ class HyperparameterGrid:
         self.h2_se = h2_se or 0.1
         self.n_snps = n_snps
         self._search_params = []
+        self._generated = {}            # grid name -> arguments of the generate_* call that built it (per-chromosome grids)
         given = dict(sigma_epsilon=(sigma_epsilon_grid, sigma_epsilon_steps), tau_beta=(tau_beta_grid, tau_beta_steps),
                      pi=(pi_grid, pi_steps), lambda_min=(lambda_min_grid, lambda_min_steps))
         for name in _ORDER:
@@ -62,6 +63,7 @@ class HyperparameterGrid:
         hi = np.log10(min(10000 / self.n_snps, max_pi))
         assert lo < hi
         self._register("pi", np.logspace(lo, hi, steps))
+        self._generated["pi"] = dict(steps=steps, max_pi=max_pi)
 
     def generate_lambda_min_grid(self, steps=5, emp_lambda_min=None):
         assert steps > 0
@@ -69,6 +71,7 @@ class HyperparameterGrid:
         if emp_lambda_min is not None:
             grid = grid * emp_lambda_min
         self._register("lambda_min", grid)
+        self._generated["lambda_min"] = dict(steps=steps)
 
     def combine_grids(self):
         names = [n for n in _ORDER if n in self._search_params and getattr(self, n) is not None]

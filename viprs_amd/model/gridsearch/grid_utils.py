@@ -94,3 +94,97 @@ def bayesian_model_average(viprs_grid_model, normalization="softmax"):
     m.fix_params = fixed
     m.n_models = 1
     return m
+
+
+# ---- one grid per chromosome (VIPRSGridPerChromosome): the CLI selects or averages per chromosome (bin/viprs_fit:534-551) ----
+def _per_chromosome_result(m):
+    from ...utils.optim import OptimizeResult
+    res = m.optim_result = OptimizeResult()
+    res.nit = max(r.nit for rs in m.optim_results.values() for r in (rs if isinstance(rs, list) else [rs]))
+    res.stop_iteration = True
+    res.success = all(r.success for rs in m.optim_results.values() for r in (rs if isinstance(rs, list) else [rs]))
+    m.n_models = 1
+    return m
+
+
+def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO"):
+    """`select_best_model` per chromosome of a fitted ``VIPRSGridPerChromosome``: every chromosome keeps ITS best grid point,
+    the model ends in ``VIPRSPerChromosome``'s result layout (``pi[c]`` ... scalars, ``pip[c]`` ... of shape (m_c,),
+    ``optim_results[c]`` one result, ``best_model_idx[c]``).  What `select_best_model` picks on each chromosome's own
+    ``VIPRSGrid`` fit, the same arrays."""
+    if criterion not in ("ELBO", "validation", "pseudo_validation"):
+        raise AssertionError(f"unknown criterion {criterion!r}")
+    if criterion == "validation":
+        raise NotImplementedError("the genotype-based validation criterion needs the reference's prediction stack")
+    m = model
+    best = {}
+    for c in m.groups:
+        ok = np.array([r.valid_optim_result for r in m.optim_results[c]])
+        if np.sum(ok) < 2:
+            raise ValueError(f"chromosome {c}: less than two models converged successfully. Cannot perform model selection.")
+        if criterion == "ELBO":
+            score = np.array(m.model_elbos[c], dtype=np.float64)
+        else:
+            vb = validation_gdl if isinstance(validation_gdl, dict) else getattr(validation_gdl, "std_beta", None)
+            if vb is None:
+                vb = getattr(m, "validation_std_beta", None)
+            if vb is None:
+                raise ValueError("Validation GWADataLoader or standardized betas from a validation set must be "
+                                 "initialized for the pseudo_validation criterion.")
+            score = np.nan_to_num(np.asarray(m.pseudo_validate(vb, chrom=c), dtype=np.float64), nan=0.0, neginf=0.0, posinf=0.0)
+            m.validation_result[c]["Pseudo_Validation_R2"] = score
+        score = score.copy()
+        score[~ok] = -np.inf
+        best[c] = int(np.argmax(score))
+    for param in (m.pip, m.post_mean_beta, m.post_var_beta, m.var_gamma, m.var_mu, m.var_tau, m.eta, m.zeta, m.q,
+                  m._log_var_tau, m.eta_diff):
+        for c in param:
+            param[c] = np.ascontiguousarray(param[c][:, best[c]])
+    for d in (m.sigma_epsilon, m._sigma_g, m.tau_beta, m.pi, m.model_elbos):
+        for c in d:
+            d[c] = d[c][best[c]]
+    m.optim_results = {c: m.optim_results[c][best[c]] for c in m.groups}
+    m.best_model_idx = best
+    return _per_chromosome_result(m)
+
+
+def bayesian_model_average_per_chromosome(model, normalization="softmax"):
+    """`bayesian_model_average` per chromosome of a fitted ``VIPRSGridPerChromosome``: the grid points of every chromosome
+    are averaged with weights from THEIR ELBOs and the chromosome's hyper-parameters follow from its averaged posterior
+    (one M-step of that chromosome's model).  ``VIPRSPerChromosome``'s result layout; ``model_weights[c]``."""
+    m = model
+    if m.n_models < 2:
+        return m
+    if normalization not in ("softmax", "sum"):
+        raise KeyError(f"Normalization scheme not recognized. Valid options are: `softmax`, `sum`. Got: {normalization}")
+    weights = {}
+    for c in m.groups:
+        valid = np.array([r.valid_optim_result for r in m.optim_results[c]])
+        if np.sum(valid) < 1:
+            raise ValueError(f"chromosome {c}: no models converged successfully. Cannot average models.")
+        keep = np.where(valid)[0]
+        elbos = np.array(m.model_elbos[c], dtype=np.float64)[keep]
+        if normalization == "softmax":
+            w = np.exp(elbos - elbos.max())
+        else:
+            w = elbos - elbos.min() + 1.0
+        w /= w.sum()
+        weights[c] = w
+        for param in (m.var_gamma, m.var_mu, m.var_tau, m.q):
+            param[c] = (param[c][:, keep] * w).sum(axis=1).astype(param[c].dtype)
+    m.eta = m.compute_eta()
+    m.zeta = m.compute_zeta()
+    m.update_posterior_moments()
+    m._log_var_tau = {c: np.log(m.var_tau[c]) for c in m.var_tau}
+    m.eta_diff = {c: np.zeros_like(e) for c, e in m.eta.items()}
+    m.model_weights = weights
+    # hyper-parameters implied by each chromosome's averaged posterior (grid_utils.py:176-183): the model's own M-step with
+    # nothing fixed, run on that chromosome alone
+    pi, tau, sig, sg = {}, {}, {}, {}
+    for c in m.groups:
+        pi[c], tau[c], sig[c], sg[c] = m.m_step_of_chromosome(c)
+    m.pi, m.tau_beta, m.sigma_epsilon, m._sigma_g = pi, tau, sig, sg
+    # (one record per chromosome: the fit of its grid point with the largest weight)
+    m.optim_results = {c: m.optim_results[c][int(np.where([r.valid_optim_result for r in m.optim_results[c]])[0][np.argmax(weights[c])])]
+                       for c in m.groups}
+    return _per_chromosome_result(m)

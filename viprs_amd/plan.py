@@ -188,7 +188,7 @@ class LDPlan:
 
     def set_active_blocks(self, active):
         """Which LD blocks the following sweeps visit: a boolean per block in SNP order (`blocks()`), None = all of them
-        (`viprs_plan_set_active_blocks`).  Spike-and-slab / mixture states; the batched grid kernel refuses a filtered plan."""
+        (`viprs_plan_set_active_blocks`).  Every kernel family sweeps the active subset, the batched grid kernel included."""
         if active is None:
             L.check(L.lib.viprs_plan_set_active_blocks(self.handle, None, 0))
             return
@@ -531,6 +531,38 @@ class DeviceState:
         out = np.zeros((self._n_sum_cols, 7 + 6 * self.width), dtype=np.float64)
         L.check(L.lib.viprs_state_sums_mixture_groups_end(self._h, _ptr(out)))
         return out
+
+    # -- SNP groups of a grid state: one set of hyper-parameters per (group, column) pair ------------
+    def prep_grid_groups(self, params):
+        """`prep_columns` per (group, column) pair: rows (group, column, logit_pi, log_tau_beta, sigma_epsilon, tau_beta,
+        one_plus_lambda); only the listed pairs' SNPs x column are rewritten."""
+        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 7)
+        L.check(L.lib.viprs_state_prep_grid_groups(self._h, int(p.shape[0]), _ptr(p)))
+
+    def sums_grid_groups_begin(self, groups, cols, one_plus_lambda):
+        """The sums of the (groups[i], cols[i]) pairs, one launch (asynchronous); `sums_grid_groups_end` collects them."""
+        n = len(groups)
+        r = np.ascontiguousarray(np.column_stack([np.asarray(groups, dtype=np.float64), np.asarray(cols, dtype=np.float64),
+                                                  np.broadcast_to(np.asarray(one_plus_lambda, dtype=np.float64), (n,))]))
+        self._n_sum_cols = n
+        L.check(L.lib.viprs_state_sums_grid_groups_begin(self._h, n, _ptr(r)))
+
+    def sums_grid_groups_end(self):
+        """(n, 11) rows in the layout of `sums_columns_end`, [0] the plain sum of gamma over the group."""
+        out = np.zeros((self._n_sum_cols, L.N_SUMS), dtype=np.float64)
+        L.check(L.lib.viprs_state_sums_grid_groups_end(self._h, _ptr(out)))
+        return out
+
+    def set_group_columns(self, active):
+        """(n_groups, width) boolean mask of the (group, column) pairs the following sweeps update (None clears it):
+        column g of group c is swept only if g is in `active_model_idx` and active[c, g] is set."""
+        if active is None:
+            L.check(L.lib.viprs_state_set_group_columns(self._h, 0, 0, None))
+            return
+        a = np.ascontiguousarray(active, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError(f"active: expected an (n_groups, width) mask, got shape {a.shape}")
+        L.check(L.lib.viprs_state_set_group_columns(self._h, int(a.shape[0]), int(a.shape[1]), _ptr(a)))
 
     # -- one model (column) of a grid state -----------------------------------------------------
     def prep_column(self, g, logit_pi, log_tau_beta, sigma_epsilon, tau_beta, one_plus_lambda):
