@@ -16,70 +16,100 @@ __global__ void reset_state_kernel(T* var_gamma, T* var_mu, int64_t n_wide, T* e
     if (i < n_vec) { eta[i] = (T)0; q[i] = (T)0; eta_diff[i] = (T)0; }
 }
 
-// VIPRS.py:400-418 on the device (float64, cast to T at the end)
-template <typename T>
-__global__ void prep_kernel(const double* __restrict__ n, int64_t m, double logit_pi, double log_tau_beta,
-                            double sigma_eps, double tau_beta, double one_plus_lambda, T* __restrict__ mu_mult,
-                            T* __restrict__ u_logs, T* __restrict__ shvt, double* __restrict__ var_tau_out,
-                            int half_not_sqrt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const double vt = n[i] * one_plus_lambda / sigma_eps + tau_beta;
-    if (var_tau_out) var_tau_out[i] = vt;              // (grid columns: not stored, the sums form it again)
-    mu_mult[i] = (T)(n[i] / (vt * sigma_eps));
-    u_logs[i] = (T)(logit_pi + 0.5 * (log_tau_beta - log(vt)));
-    shvt[i] = half_not_sqrt ? (T)(0.5 * vt) : (T)sqrt(0.5 * vt);     // e_step_grid takes var_tau / 2 (e_step.hpp:616)
-}
+// ---- the EM iteration around the sweep, as ROWS: a row is one model over a contiguous SNP range [i0, i1) of one column
+// (the whole plan: one row over [0, m); a grid column: a row over [0, m) at the column's offset; an SNP group: a row over
+// [group_start[g], group_start[g+1]); a grid (group, column) pair: both).  blockIdx.y picks the row -- of a table staged on
+// the device, or the single row a one-model call passes as a kernel argument (`rows` == nullptr).  The kernels read the row
+// from one place or the other in two branches: a select between the two addresses makes the row's fields per-lane values
+// (sums_mixture_kernel: 40 more VGPRs, one wave per SIMD less), a local copy of a mixture row indexed by k goes to scratch.
 
-// the same for several columns of a grid state in one launch: blockIdx.y picks a row of `params`
-// (column, logit_pi, log_tau_beta, sigma_eps, tau_beta, one_plus_lambda)
-// (var_tau itself is not stored for a grid state: m x G doubles to write here and to read back in the sums -- the sums
-//  kernel forms it again from n_j and the column's scalars, the same expression, the same bits)
-template <typename T>
-__global__ void prep_columns_kernel(const double* __restrict__ n, int64_t m, const double* __restrict__ params,
-                                    T* __restrict__ mu_mult, T* __restrict__ u_logs, T* __restrict__ shvt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const double* __restrict__ p = params + 6 * (int64_t)blockIdx.y;
-    const int64_t off = (int64_t)p[0] * m;
-    const double logit_pi = p[1], log_tau_beta = p[2], sigma_eps = p[3], tau_beta = p[4], one_plus_lambda = p[5];
-    const double vt = n[i] * one_plus_lambda / sigma_eps + tau_beta;
-    mu_mult[off + i] = (T)(n[i] / (vt * sigma_eps));
-    u_logs[off + i] = (T)(logit_pi + 0.5 * (log_tau_beta - log(vt)));
-    shvt[off + i] = (T)(0.5 * vt);                                    // e_step_grid takes var_tau / 2 (e_step.hpp:616)
-}
+// prep: VIPRS.py:400-418 on the device (float64, cast to T at the end)
+struct PrepRow {
+    int64_t i0, i1, off;                           // SNPs [i0, i1) of the column at element offset `off`
+    double logit_pi, log_tau_beta, sigma_eps, tau_beta, one_plus_lambda;
+};
 
-// the same for SNP GROUPS of a spike-and-slab state (one model per chromosome in one plan): blockIdx.y picks a row of
-// `params` (group, logit_pi, log_tau_beta, sigma_eps, tau_beta, one_plus_lambda); only the group's SNPs are written
-template <typename T>
-__global__ void prep_groups_kernel(const double* __restrict__ n, const int64_t* __restrict__ gstart,
-                                   const double* __restrict__ params, T* __restrict__ mu_mult, T* __restrict__ u_logs,
-                                   T* __restrict__ shvt, double* __restrict__ var_tau_out) {
-    const double* __restrict__ p = params + 6 * (int64_t)blockIdx.y;
-    const int g = (int)p[0];
-    const double logit_pi = p[1], log_tau_beta = p[2], sigma_eps = p[3], tau_beta = p[4], one_plus_lambda = p[5];
-    const int64_t end = gstart[g + 1];
-    for (int64_t i = gstart[g] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (int64_t)gridDim.x * blockDim.x) {
-        const double vt = n[i] * one_plus_lambda / sigma_eps + tau_beta;
-        var_tau_out[i] = vt;
-        mu_mult[i] = (T)(n[i] / (vt * sigma_eps));
-        u_logs[i] = (T)(logit_pi + 0.5 * (log_tau_beta - log(vt)));
-        shvt[i] = (T)sqrt(0.5 * vt);
+// spike-and-slab: var_tau stored, sqrt(var_tau / 2) written.  GRID (columns of a grid state): var_tau / 2 written
+// (e_step_grid takes it, e_step.hpp:616) and var_tau not stored -- m x G doubles to write here and to read back in the
+// sums, which form it again from n_j and the row's scalars, the same expression, the same bits
+template <typename T, bool GRID>
+__global__ void prep_kernel(const double* __restrict__ n, PrepRow one, const PrepRow* __restrict__ rows,
+                            T* __restrict__ mu_mult, T* __restrict__ u_logs, T* __restrict__ shvt,
+                            double* __restrict__ var_tau) {
+    PrepRow r;
+    if (rows) r = rows[blockIdx.y];
+    else r = one;
+    for (int64_t i = r.i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < r.i1; i += (int64_t)gridDim.x * blockDim.x) {
+        const double vt = n[i] * r.one_plus_lambda / r.sigma_eps + r.tau_beta;
+        mu_mult[r.off + i] = (T)(n[i] / (vt * r.sigma_eps));
+        u_logs[r.off + i] = (T)(r.logit_pi + 0.5 * (r.log_tau_beta - log(vt)));
+        if (GRID) {
+            shvt[r.off + i] = (T)(0.5 * vt);
+        } else {
+            shvt[r.off + i] = (T)sqrt(0.5 * vt);
+            var_tau[i] = vt;
+        }
     }
 }
 
-constexpr int kSumsBlock = 256;
-constexpr int kNSums = VIPRS_N_SUMS;
-constexpr int kSumsMaxBlocks = 1024;
-// workgroups of the reduction over `count` SNPs (the same for a whole plan and for one group of it: a group's sums are
-// bit-identical to those of a plan that holds only that group)
-__host__ __device__ inline int sums_blocks(int64_t count) {
-    const int64_t nb = (count + kSumsBlock - 1) / kSumsBlock;
-    return (int)(nb < kSumsMaxBlocks ? nb : kSumsMaxBlocks);
+// ---- mixture (VIPRSMix.py:169-225 prep, :227-260 M-step, elbo) ----
+constexpr int kMixResidentK = 8;                                  // = kPanelMaxK: the lane-parallel panel chain
+constexpr int kMixSums(int K) { return 7 + 6 * K; }               // s[0..5] | kv[6][K] | max |eta_diff|
+struct MixPrepRow {
+    int64_t i0, i1;
+    double log_null_pi, sigma_eps, one_plus_lambda;
+    double logit_pi[kMixResidentK], log_tau[kMixResidentK], tau[kMixResidentK];
+};
+
+// per SNP and component (C-order (m, K)): var_tau = n (1 + lambda) / sigma_eps + tau_k and the three E-step inputs
+template <typename T>
+__device__ __forceinline__ void prep_mixture_body(const double* __restrict__ n, int K, const MixPrepRow& r, T* __restrict__ mu_mult,
+                                                  T* __restrict__ u_logs, T* __restrict__ shvt, T* __restrict__ lnp,
+                                                  double* __restrict__ var_tau) {
+    for (int64_t i = r.i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < r.i1; i += (int64_t)gridDim.x * blockDim.x) {
+        lnp[i] = (T)r.log_null_pi;
+        for (int k = 0; k < K; ++k) {
+            const double vt = n[i] * r.one_plus_lambda / r.sigma_eps + r.tau[k];
+            var_tau[i * K + k] = vt;
+            mu_mult[i * K + k] = (T)(n[i] / (vt * r.sigma_eps));
+            u_logs[i * K + k] = (T)(r.logit_pi[k] + 0.5 * (r.log_tau[k] - log(vt)));
+            shvt[i * K + k] = (T)sqrt(0.5 * vt);
+        }
+    }
+}
+template <typename T>
+__global__ void prep_mixture_kernel(const double* __restrict__ n, int K, MixPrepRow one, const MixPrepRow* __restrict__ rows,
+                                    T* __restrict__ mu_mult, T* __restrict__ u_logs, T* __restrict__ shvt,
+                                    T* __restrict__ lnp, double* __restrict__ var_tau) {
+    if (rows) prep_mixture_body(n, K, rows[blockIdx.y], mu_mult, u_logs, shvt, lnp, var_tau);
+    else prep_mixture_body(n, K, one, mu_mult, u_logs, shvt, lnp, var_tau);
 }
 
-// stage 1: per-workgroup partial sums (fixed assignment of elements to threads, tree reduction in
-// LDS: deterministic); stage 2 adds the partials in index order.  `sums_body`: workgroup `bx` of `nb` over SNPs [i0, i1).
+// ---- M-step / ELBO sums: stage 1, per-workgroup partials (fixed assignment of elements to threads, fixed tree);
+// stage 2 (sums_final_kernel) adds the partials of a row in index order.  The workgroup count of a row fixes its summation
+// order: `sums_blocks` for spike-and-slab and mixture rows, `grid_sums_blocks` for grid rows -- the counts a plan that
+// holds only the row's SNPs uses, so a group's or pair's sums are bit-identical to those of a plan of its own.
+constexpr int kSumsBlock = 256;
+constexpr int kNSums = VIPRS_N_SUMS;
+__host__ __device__ inline int sums_blocks(int64_t count) {
+    const int64_t nb = (count + kSumsBlock - 1) / kSumsBlock;
+    return (int)(nb < 1024 ? nb : 1024);
+}
+__host__ __device__ inline int grid_sums_blocks(int64_t count) {
+    const int64_t nb = (count + kSumsBlock - 1) / kSumsBlock;
+    return (int)(nb < 256 ? nb : 256);
+}
+
+struct SumsRow {
+    int64_t i0, i1, off;                           // SNPs [i0, i1) of the column at element offset `off`
+    int nb;                                        // workgroups of the row
+    int weighted;                                  // d_weight applies to sum [0] (the whole plan / a grid column)
+    int form_vt;                                   // grid: var_tau formed from n as the last prep did, from vt[] =
+    double vt[3];                                  //   (one_plus_lambda, sigma_eps, tau_beta); otherwise the stored var_tau
+    double one_plus_lambda;
+};
+
+// `sums_body`: workgroup `bx` of `nb` over SNPs [i0, i1), tree reduction in LDS
 template <typename T>
 __device__ __forceinline__ void sums_body(int64_t i0, int64_t i1, int nb, int bx, const T* __restrict__ gam,
                                           const T* __restrict__ mu, const T* __restrict__ eta, const T* __restrict__ q,
@@ -125,111 +155,26 @@ __device__ __forceinline__ void sums_body(int64_t i0, int64_t i1, int nb, int bx
     if (threadIdx.x < kNSums) out[threadIdx.x] = red[threadIdx.x][0];
 }
 
+// spike-and-slab / grid rows: row y's workgroups write their partials at slots y * gridDim.x + x (the rest of the row leaves)
 template <typename T>
-__global__ __launch_bounds__(kSumsBlock) void sums_kernel(int64_t m, const T* __restrict__ gam, const T* __restrict__ mu,
+__global__ __launch_bounds__(kSumsBlock) void sums_kernel(SumsRow one, const SumsRow* __restrict__ rows,
+                                                          const T* __restrict__ gam, const T* __restrict__ mu,
                                                           const T* __restrict__ eta, const T* __restrict__ q,
                                                           const T* __restrict__ ed, const T* __restrict__ beta,
-                                                          const double* __restrict__ var_tau, double one_plus_lambda,
-                                                          const double* __restrict__ weight, double* __restrict__ partials,
-                                                          const double* __restrict__ cols = nullptr) {
-    if (cols) {
-        // columns of a grid state, one per blockIdx.y: a row of `cols` = (column, one_plus_lambda, and the scalars the
-        // column's last prep built var_tau from: one_plus_lambda, sigma_eps, tau_beta); `var_tau` is the per-SNP n here
-        const double* __restrict__ c = cols + 5 * (int64_t)blockIdx.y;
-        const int64_t off = (int64_t)c[0] * m;
-        gam += off; mu += off; eta += off; q += off; ed += off;
-        partials += (int64_t)blockIdx.y * gridDim.x * kNSums;
-        sums_body<T>(0, m, (int)gridDim.x, (int)blockIdx.x, gam, mu, eta, q, ed, beta, nullptr, c[1], weight,
-                     partials + (int64_t)blockIdx.x * kNSums, var_tau, c[2], c[3], c[4]);
-        return;
-    }
-    sums_body<T>(0, m, (int)gridDim.x, (int)blockIdx.x, gam, mu, eta, q, ed, beta, var_tau, one_plus_lambda, weight,
-                 partials + (int64_t)blockIdx.x * kNSums);
-}
-
-// the sums of SNP groups of a spike-and-slab state: blockIdx.y picks a row (group, one_plus_lambda) of `rows`; group g is
-// reduced by sums_blocks(its SNPs) workgroups exactly as a plan of its own would be (the rest of the row's grid leaves)
-template <typename T>
-__global__ __launch_bounds__(kSumsBlock) void sums_groups_kernel(const int64_t* __restrict__ gstart, const double* __restrict__ rows,
-                                                                 const T* __restrict__ gam, const T* __restrict__ mu,
-                                                                 const T* __restrict__ eta, const T* __restrict__ q,
-                                                                 const T* __restrict__ ed, const T* __restrict__ beta,
-                                                                 const double* __restrict__ var_tau, double* __restrict__ partials) {
-    const int g = (int)rows[2 * blockIdx.y];
-    const int64_t i0 = gstart[g], i1 = gstart[g + 1];
-    const int nb = sums_blocks(i1 - i0);
-    if ((int)blockIdx.x >= nb) return;
-    sums_body<T>(i0, i1, nb, (int)blockIdx.x, gam, mu, eta, q, ed, beta, var_tau, rows[2 * blockIdx.y + 1], nullptr,
-                 partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kNSums);
-}
-
-// one wave per sum: lane l adds the partials of blocks l, l + 64, ... in order, then a fixed xor-shuffle
-// tree combines the 64 lanes -- a deterministic order whatever the timing
-__global__ void sums_final_kernel(const double* __restrict__ partials, int n_blocks, double* __restrict__ out) {
-    partials += (int64_t)blockIdx.x * n_blocks * kNSums;            // one workgroup per column (grid states)
-    out += (int64_t)blockIdx.x * kNSums;
-    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (k >= kNSums) return;
-    const bool is_max = (k == kNSums - 1);
-    double a = 0.0;
-    for (int b = lane; b < n_blocks; b += 64) {
-        const double v = partials[(int64_t)b * kNSums + k];
-        a = is_max ? fmax(a, v) : a + v;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(a, off, 64);
-        a = is_max ? fmax(a, o) : a + o;
-    }
-    if (lane == 0) out[k] = a;
-}
-
-// the same per group: workgroup y adds the sums_blocks(group's SNPs) partials of row y (`stride` slots per row)
-__global__ void sums_final_groups_kernel(const double* __restrict__ partials, int stride, const int64_t* __restrict__ gstart,
-                                         const double* __restrict__ rows, double* __restrict__ out) {
-    const int g = (int)rows[2 * blockIdx.x];
-    const int n_blocks = sums_blocks(gstart[g + 1] - gstart[g]);
-    partials += (int64_t)blockIdx.x * stride * kNSums;
-    out += (int64_t)blockIdx.x * kNSums;
-    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (k >= kNSums) return;
-    const bool is_max = (k == kNSums - 1);
-    double a = 0.0;
-    for (int b = lane; b < n_blocks; b += 64) {
-        const double v = partials[(int64_t)b * kNSums + k];
-        a = is_max ? fmax(a, v) : a + v;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(a, off, 64);
-        a = is_max ? fmax(a, o) : a + o;
-    }
-    if (lane == 0) out[k] = a;
-}
-
-// ---- device-resident EM iteration of the mixture model (VIPRSMix.py:169-225 prep, :227-260 M-step, elbo) ----
-constexpr int kMixResidentK = 8;                                  // = kPanelMaxK: the lane-parallel panel chain
-constexpr int kMixSums(int K) { return 7 + 6 * K; }               // s[0..5] | kv[6][K] | max |eta_diff|
-struct MixPrepArgs { double logit_pi[kMixResidentK], log_tau[kMixResidentK], tau[kMixResidentK]; };
-
-// per SNP and component (C-order (m, K)): var_tau = n (1 + lambda) / sigma_eps + tau_k and the three E-step inputs
-template <typename T>
-__global__ void prep_mixture_kernel(const double* __restrict__ n, int64_t m, int K, MixPrepArgs a, double sigma_eps,
-                                    double one_plus_lambda, double log_null_pi, T* __restrict__ mu_mult,
-                                    T* __restrict__ u_logs, T* __restrict__ shvt, T* __restrict__ lnp,
-                                    double* __restrict__ var_tau_out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    lnp[i] = (T)log_null_pi;
-    for (int k = 0; k < K; ++k) {
-        const double vt = n[i] * one_plus_lambda / sigma_eps + a.tau[k];
-        var_tau_out[i * K + k] = vt;
-        mu_mult[i * K + k] = (T)(n[i] / (vt * sigma_eps));
-        u_logs[i * K + k] = (T)(a.logit_pi[k] + 0.5 * (a.log_tau[k] - log(vt)));
-        shvt[i * K + k] = (T)sqrt(0.5 * vt);
-    }
+                                                          const double* __restrict__ var_tau, const double* __restrict__ n_snp,
+                                                          const double* __restrict__ weight, double* __restrict__ partials) {
+    SumsRow r;
+    if (rows) r = rows[blockIdx.y];
+    else r = one;
+    if ((int)blockIdx.x >= r.nb) return;
+    sums_body<T>(r.i0, r.i1, r.nb, (int)blockIdx.x, gam + r.off, mu + r.off, eta + r.off, q + r.off, ed + r.off, beta,
+                 r.form_vt ? nullptr : var_tau, r.one_plus_lambda, r.weighted ? weight : nullptr,
+                 partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kNSums, r.form_vt ? n_snp : nullptr, r.vt[0],
+                 r.vt[1], r.vt[2]);
 }
 
 // VIPRSMix._partial_sums on the device (float64): per-workgroup partials, fixed order.  `sums_mixture_body`: workgroup `bx`
-// of `nb` over SNPs [i0, i1) -- a plan's SNPs, or one SNP group of it reduced exactly as a plan of its own would be.
+// of `nb` over SNPs [i0, i1).
 template <typename T>
 __device__ __forceinline__ void sums_mixture_body(int64_t i0, int64_t i1, int nb, int bx, int K, const T* __restrict__ gam,
                                                   const T* __restrict__ mu, const T* __restrict__ eta,
@@ -296,87 +241,36 @@ __device__ __forceinline__ void sums_mixture_body(int64_t i0, int64_t i1, int nb
     }
 }
 
+// mixture rows (the stored var_tau, no per-SNP weight): partial slots as in sums_kernel
 template <typename T>
-__global__ __launch_bounds__(kSumsBlock) void sums_mixture_kernel(int64_t m, int K, const T* __restrict__ gam,
-                                                                  const T* __restrict__ mu, const T* __restrict__ eta,
-                                                                  const T* __restrict__ q, const T* __restrict__ ed,
-                                                                  const T* __restrict__ beta, const double* __restrict__ var_tau,
-                                                                  const double* __restrict__ log_var_tau0, double one_plus_lambda,
+__global__ __launch_bounds__(kSumsBlock) void sums_mixture_kernel(int K, SumsRow one, const SumsRow* __restrict__ rows,
+                                                                  const T* __restrict__ gam, const T* __restrict__ mu,
+                                                                  const T* __restrict__ eta, const T* __restrict__ q,
+                                                                  const T* __restrict__ ed, const T* __restrict__ beta,
+                                                                  const double* __restrict__ var_tau,
+                                                                  const double* __restrict__ log_var_tau0,
                                                                   double* __restrict__ partials) {
-    sums_mixture_body<T>(0, m, (int)gridDim.x, (int)blockIdx.x, K, gam, mu, eta, q, ed, beta, var_tau, log_var_tau0, one_plus_lambda,
-                         partials + (int64_t)blockIdx.x * kMixSums(K));
+    SumsRow r;
+    if (rows) r = rows[blockIdx.y];
+    else r = one;
+    if ((int)blockIdx.x >= r.nb) return;
+    sums_mixture_body<T>(r.i0, r.i1, r.nb, (int)blockIdx.x, K, gam, mu, eta, q, ed, beta, var_tau, log_var_tau0,
+                         r.one_plus_lambda, partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kMixSums(K));
 }
 
-// SNP groups of a mixture state (one model per chromosome in one plan): blockIdx.y picks a row (group, one_plus_lambda)
-template <typename T>
-__global__ __launch_bounds__(kSumsBlock) void sums_mixture_groups_kernel(const int64_t* __restrict__ gstart, const double* __restrict__ rows,
-                                                                         int K, const T* __restrict__ gam, const T* __restrict__ mu,
-                                                                         const T* __restrict__ eta, const T* __restrict__ q,
-                                                                         const T* __restrict__ ed, const T* __restrict__ beta,
-                                                                         const double* __restrict__ var_tau,
-                                                                         const double* __restrict__ log_var_tau0,
-                                                                         double* __restrict__ partials) {
-    const int g = (int)rows[2 * blockIdx.y];
-    const int64_t i0 = gstart[g], i1 = gstart[g + 1];
-    const int nb = sums_blocks(i1 - i0);
-    if ((int)blockIdx.x >= nb) return;
-    sums_mixture_body<T>(i0, i1, nb, (int)blockIdx.x, K, gam, mu, eta, q, ed, beta, var_tau, log_var_tau0, rows[2 * blockIdx.y + 1],
-                         partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kMixSums(K));
-}
-
-// per-SNP inputs of the groups listed in `params`: rows of 4 + 3 K doubles (group, log_null_pi, sigma_eps, one_plus_lambda,
-// logit_pi[K], log_tau_beta[K], tau_beta[K]); blockIdx.y picks the row, only the group's SNPs are written
-template <typename T>
-__global__ void prep_mixture_groups_kernel(const double* __restrict__ n, const int64_t* __restrict__ gstart, int K,
-                                           const double* __restrict__ params, T* __restrict__ mu_mult, T* __restrict__ u_logs,
-                                           T* __restrict__ shvt, T* __restrict__ lnp, double* __restrict__ var_tau_out) {
-    const double* __restrict__ p = params + (int64_t)(4 + 3 * K) * blockIdx.y;
-    const int g = (int)p[0];
-    const double log_null_pi = p[1], sigma_eps = p[2], one_plus_lambda = p[3];
-    const double* __restrict__ logit_pi = p + 4;
-    const double* __restrict__ log_tau = p + 4 + K;
-    const double* __restrict__ tau = p + 4 + 2 * K;
-    const int64_t end = gstart[g + 1];
-    for (int64_t i = gstart[g] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (int64_t)gridDim.x * blockDim.x) {
-        lnp[i] = (T)log_null_pi;
-        for (int k = 0; k < K; ++k) {
-            const double vt = n[i] * one_plus_lambda / sigma_eps + tau[k];
-            var_tau_out[i * K + k] = vt;
-            mu_mult[i * K + k] = (T)(n[i] / (vt * sigma_eps));
-            u_logs[i * K + k] = (T)(logit_pi[k] + 0.5 * (log_tau[k] - log(vt)));
-            shvt[i * K + k] = (T)sqrt(0.5 * vt);
-        }
-    }
-}
-
-// one workgroup (one wave) per sum over the per-block partials; the last sum is a maximum
-__global__ void sums_final_generic_kernel(const double* __restrict__ partials, int n_blocks, int n_sums,
-                                          double* __restrict__ out) {
-    const int k = blockIdx.x, lane = threadIdx.x;
-    const bool is_max = (k == n_sums - 1);
-    double a = 0.0;
-    for (int b = lane; b < n_blocks; b += 64) {
-        const double v = partials[(int64_t)b * n_sums + k];
-        a = is_max ? fmax(a, v) : a + v;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(a, off, 64);
-        a = is_max ? fmax(a, o) : a + o;
-    }
-    if (lane == 0) out[k] = a;
-}
-
-// the same per group: workgroup (k, y) adds the sums_blocks(group's SNPs) partials of sum k of row y (`stride` slots per row)
-__global__ void sums_final_generic_groups_kernel(const double* __restrict__ partials, int stride, int n_sums,
-                                                 const int64_t* __restrict__ gstart, const double* __restrict__ rows,
-                                                 double* __restrict__ out) {
-    const int g = (int)rows[2 * blockIdx.y];
-    const int n_blocks = sums_blocks(gstart[g + 1] - gstart[g]);
+// stage 2, every family: workgroup (k, y) is one wave adding sum k over the `nb` partials of row y (`stride` slots per row):
+// lane l adds the partials of workgroups l, l + 64, ... in order, then a fixed xor-shuffle tree combines the 64 lanes -- a
+// deterministic order whatever the timing; the last sum of a row is a maximum
+__global__ void sums_final_kernel(const double* __restrict__ partials, int stride, int n_sums, SumsRow one,
+                                  const SumsRow* __restrict__ rows, double* __restrict__ out) {
+    int nb;
+    if (rows) nb = rows[blockIdx.y].nb;
+    else nb = one.nb;
     partials += (int64_t)blockIdx.y * stride * n_sums;
     const int k = blockIdx.x, lane = threadIdx.x;
     const bool is_max = (k == n_sums - 1);
     double a = 0.0;
-    for (int b = lane; b < n_blocks; b += 64) {
+    for (int b = lane; b < nb; b += 64) {
         const double v = partials[(int64_t)b * n_sums + k];
         a = is_max ? fmax(a, v) : a + v;
     }
@@ -385,74 +279,6 @@ __global__ void sums_final_generic_groups_kernel(const double* __restrict__ part
         a = is_max ? fmax(a, o) : a + o;
     }
     if (lane == 0) out[(int64_t)blockIdx.y * n_sums + k] = a;
-}
-
-// ---- SNP groups of a GRID state: one set of hyper-parameters per (group, column) pair (one VIPRSGrid per chromosome) ----
-// workgroups of the reduction of one column over `count` SNPs: what viprs_state_sums_columns uses for a plan of that size
-__host__ __device__ inline int grid_sums_blocks(int64_t count) {
-    const int64_t nb = (count + kSumsBlock - 1) / kSumsBlock;
-    return (int)(nb < 256 ? nb : 256);
-}
-
-// prep_columns_kernel for (group, column) pairs: blockIdx.y picks a row of `params` (group, column, logit_pi,
-// log_tau_beta, sigma_eps, tau_beta, one_plus_lambda); only the group's SNPs of that column are written
-template <typename T>
-__global__ void prep_grid_groups_kernel(const double* __restrict__ n, int64_t m, const int64_t* __restrict__ gstart,
-                                        const double* __restrict__ params, T* __restrict__ mu_mult, T* __restrict__ u_logs,
-                                        T* __restrict__ shvt) {
-    const double* __restrict__ p = params + 7 * (int64_t)blockIdx.y;
-    const int g = (int)p[0];
-    const int64_t off = (int64_t)p[1] * m;
-    const double logit_pi = p[2], log_tau_beta = p[3], sigma_eps = p[4], tau_beta = p[5], one_plus_lambda = p[6];
-    const int64_t end = gstart[g + 1];
-    for (int64_t i = gstart[g] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (int64_t)gridDim.x * blockDim.x) {
-        const double vt = n[i] * one_plus_lambda / sigma_eps + tau_beta;
-        mu_mult[off + i] = (T)(n[i] / (vt * sigma_eps));
-        u_logs[off + i] = (T)(logit_pi + 0.5 * (log_tau_beta - log(vt)));
-        shvt[off + i] = (T)(0.5 * vt);                                    // e_step_grid takes var_tau / 2 (e_step.hpp:616)
-    }
-}
-
-// the sums of (group, column) pairs: blockIdx.y picks a row (group, column, one_plus_lambda, and the scalars the pair's last
-// prep built var_tau from: one_plus_lambda, sigma_eps, tau_beta); the pair is reduced by grid_sums_blocks(group's SNPs)
-// workgroups in the element order of sums_kernel over a plan that holds only the group
-template <typename T>
-__global__ __launch_bounds__(kSumsBlock) void sums_grid_groups_kernel(int64_t m, const int64_t* __restrict__ gstart,
-                                                                      const double* __restrict__ rows, const T* __restrict__ gam,
-                                                                      const T* __restrict__ mu, const T* __restrict__ eta,
-                                                                      const T* __restrict__ q, const T* __restrict__ ed,
-                                                                      const T* __restrict__ beta, const double* __restrict__ n_snp,
-                                                                      double* __restrict__ partials) {
-    const double* __restrict__ r = rows + 6 * (int64_t)blockIdx.y;
-    const int g = (int)r[0];
-    const int64_t off = (int64_t)r[1] * m;
-    const int64_t i0 = gstart[g], i1 = gstart[g + 1];
-    const int nb = grid_sums_blocks(i1 - i0);
-    if ((int)blockIdx.x >= nb) return;
-    sums_body<T>(i0, i1, nb, (int)blockIdx.x, gam + off, mu + off, eta + off, q + off, ed + off, beta, nullptr, r[2], nullptr,
-                 partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kNSums, n_snp, r[3], r[4], r[5]);
-}
-
-// sums_final_kernel per pair: workgroup y adds the grid_sums_blocks(group's SNPs) partials of row y (`stride` slots per row)
-__global__ void sums_final_grid_groups_kernel(const double* __restrict__ partials, int stride, const int64_t* __restrict__ gstart,
-                                              const double* __restrict__ rows, double* __restrict__ out) {
-    const int g = (int)rows[6 * blockIdx.x];
-    const int n_blocks = grid_sums_blocks(gstart[g + 1] - gstart[g]);
-    partials += (int64_t)blockIdx.x * stride * kNSums;
-    out += (int64_t)blockIdx.x * kNSums;
-    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (k >= kNSums) return;
-    const bool is_max = (k == kNSums - 1);
-    double a = 0.0;
-    for (int b = lane; b < n_blocks; b += 64) {
-        const double v = partials[(int64_t)b * kNSums + k];
-        a = is_max ? fmax(a, v) : a + v;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(a, off, 64);
-        a = is_max ? fmax(a, o) : a + o;
-    }
-    if (lane == 0) out[k] = a;
 }
 
 }  // namespace
@@ -562,104 +388,211 @@ int check_device_error(viprs_plan* P) {
 }
 }  // namespace viprs
 
-// A rank whose plan holds no SNP still takes part in the collective of viprs_state_set_comm: it contributes zeros.
-static int sums_enqueue_empty(viprs_state* S, int n, int group) {
+// ---- host side of the rows: staging, the launchers, the reduction in flight ----------------------------------------------
+// Row tables of the batched calls go through ONE pinned staging area (prep rows, then sums rows) and one H2D copy per call;
+// the one-model calls pass their row as a kernel argument.
+static size_t prep_row_bytes(const viprs_state* S) {
+    return S->model_kind == VIPRS_MODEL_MIXTURE ? sizeof(MixPrepRow) : sizeof(PrepRow);
+}
+static SumsRow* sums_staging(const viprs_state* S) {
+    return reinterpret_cast<SumsRow*>(S->h_rows + S->rows_cap * prep_row_bytes(S));
+}
+
+// room for `n` rows (grown to the most a call can list: one per group, or per (group, column) pair / column of a grid state)
+static int row_buffers(viprs_state* S, int n) {
+    if ((size_t)n <= S->rows_cap) return VIPRS_OK;
     viprs_plan* P = S->plan;
-    HIP_TRY(hipSetDevice(P->device));
-    if (S->d_sums.n < (size_t)n) HIP_TRY(S->d_sums.alloc((size_t)n));
-    if (S->h_sums_cap < (size_t)n + 1) {
+    const size_t cap = std::max<size_t>((size_t)n, (size_t)std::max(1, S->n_groups) *
+                                                       (S->model_kind == VIPRS_MODEL_GRID ? S->width : 1));
+    HIP_TRY(hipStreamSynchronize(P->stream));                 // nothing in flight reads the old buffers
+    HIP_TRY(S->d_prep_rows.alloc(cap * prep_row_bytes(S)));
+    HIP_TRY(S->d_sum_rows.alloc(cap * sizeof(SumsRow)));
+    if (S->h_rows) HIP_TRY(hipHostFree(S->h_rows));
+    S->h_rows = nullptr;
+    S->rows_cap = 0;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_rows), cap * (prep_row_bytes(S) + sizeof(SumsRow)),
+                          hipHostMallocDefault));
+    S->rows_cap = cap;
+    return VIPRS_OK;
+}
+
+// the pinned staging of a batched prep's `n` rows, free once the previous batched prep launch has read its own
+template <typename Row>
+static int prep_staging(viprs_state* S, int n, Row** h) {
+    const int rc = row_buffers(S, n);
+    if (rc != VIPRS_OK) return rc;
+    if (!S->ev_prep) HIP_TRY(hipEventCreateWithFlags(&S->ev_prep, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(S->ev_prep));
+    *h = reinterpret_cast<Row*>(S->h_rows);
+    return VIPRS_OK;
+}
+
+// grid of a prep launch: rows along y, the longest row's SNPs along x
+template <typename Row>
+static dim3 prep_grid(int n, const Row* rows) {
+    int64_t longest = 0;
+    for (int i = 0; i < n; ++i) longest = std::max(longest, rows[i].i1 - rows[i].i0);
+    return dim3((unsigned)std::max<int64_t>(1, (longest + 255) / 256), (unsigned)n);
+}
+
+// spike-and-slab / grid prep of `one` (kernel argument) or of the `n` rows in the pinned staging (one H2D copy)
+static int prep_launch(viprs_state* S, int n, const PrepRow* one) {
+    viprs_plan* P = S->plan;
+    const PrepRow* h = one ? one : reinterpret_cast<const PrepRow*>(S->h_rows);
+    const PrepRow* rows = one ? nullptr : reinterpret_cast<const PrepRow*>(S->d_prep_rows.p);
+    if (!one) HIP_TRY(hipMemcpyAsync(S->d_prep_rows.p, h, n * sizeof(PrepRow), hipMemcpyHostToDevice, P->stream));
+    const dim3 grid = prep_grid(n, h);
+    const bool g = S->model_kind == VIPRS_MODEL_GRID;
+#define VIPRS_PREP_ARGS(T)                                                                                                    \
+    S->d_n.p, *h, rows, (T*)S->f[VIPRS_FIELD_MU_MULT].p, (T*)S->f[VIPRS_FIELD_U_LOGS].p,                                     \
+        (T*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p, S->d_var_tau.p
+    if (S->float_dtype == VIPRS_F32 && g) prep_kernel<float, true><<<grid, 256, 0, P->stream>>>(VIPRS_PREP_ARGS(float));
+    else if (S->float_dtype == VIPRS_F32) prep_kernel<float, false><<<grid, 256, 0, P->stream>>>(VIPRS_PREP_ARGS(float));
+    else if (g) prep_kernel<double, true><<<grid, 256, 0, P->stream>>>(VIPRS_PREP_ARGS(double));
+    else prep_kernel<double, false><<<grid, 256, 0, P->stream>>>(VIPRS_PREP_ARGS(double));
+#undef VIPRS_PREP_ARGS
+    HIP_TRY(hipGetLastError());
+    if (!one) HIP_TRY(hipEventRecord(S->ev_prep, P->stream));
+    return VIPRS_OK;
+}
+
+// the same for a mixture state
+static int prep_mixture_launch(viprs_state* S, int n, const MixPrepRow* one) {
+    viprs_plan* P = S->plan;
+    const int K = S->width;
+    if (S->d_var_tau.n < (size_t)P->m * K) {
+        HIP_TRY(hipStreamSynchronize(P->stream));
+        HIP_TRY(S->d_var_tau.alloc((size_t)P->m * K));
+    }
+    const MixPrepRow* h = one ? one : reinterpret_cast<const MixPrepRow*>(S->h_rows);
+    const MixPrepRow* rows = one ? nullptr : reinterpret_cast<const MixPrepRow*>(S->d_prep_rows.p);
+    if (!one) HIP_TRY(hipMemcpyAsync(S->d_prep_rows.p, h, n * sizeof(MixPrepRow), hipMemcpyHostToDevice, P->stream));
+    const dim3 grid = prep_grid(n, h);
+    if (S->float_dtype == VIPRS_F32)
+        prep_mixture_kernel<float><<<grid, 256, 0, P->stream>>>(
+            S->d_n.p, K, *h, rows, (float*)S->f[VIPRS_FIELD_MU_MULT].p, (float*)S->f[VIPRS_FIELD_U_LOGS].p,
+            (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p, (float*)S->f[VIPRS_FIELD_LOG_NULL_PI].p, S->d_var_tau.p);
+    else
+        prep_mixture_kernel<double><<<grid, 256, 0, P->stream>>>(
+            S->d_n.p, K, *h, rows, (double*)S->f[VIPRS_FIELD_MU_MULT].p, (double*)S->f[VIPRS_FIELD_U_LOGS].p,
+            (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p, (double*)S->f[VIPRS_FIELD_LOG_NULL_PI].p, S->d_var_tau.p);
+    HIP_TRY(hipGetLastError());
+    if (!one) HIP_TRY(hipEventRecord(S->ev_prep, P->stream));
+    return VIPRS_OK;
+}
+
+// one row of sums: SNPs [i0, i1) of column `col`; `vt`: the scalars of the grid column's / pair's last prep (var_tau is
+// formed from them, the reduction takes grid_sums_blocks workgroups), nullptr: the stored var_tau, sums_blocks workgroups
+static SumsRow sums_row(const viprs_state* S, int64_t i0, int64_t i1, int64_t col, double one_plus_lambda, bool weighted,
+                        const double* vt) {
+    SumsRow r{};
+    r.i0 = i0;
+    r.i1 = i1;
+    r.off = col * S->plan->m;
+    r.nb = vt ? grid_sums_blocks(i1 - i0) : sums_blocks(i1 - i0);
+    r.weighted = weighted;
+    r.one_plus_lambda = one_plus_lambda;
+    if (vt) {
+        r.form_vt = 1;
+        for (int k = 0; k < 3; ++k) r.vt[k] = vt[k];
+    }
+    return r;
+}
+
+// d_partials, d_sums and the pinned landing buffer h_sums: `total` sums + the plan's device error word (no second
+// synchronisation)
+static int sums_buffers(viprs_state* S, size_t partials, size_t total) {
+    if (S->d_partials.n < partials) HIP_TRY(S->d_partials.alloc(partials));
+    if (S->d_sums.n < total) HIP_TRY(S->d_sums.alloc(total));
+    if (S->h_sums_cap < total + 1) {
         if (S->h_sums) HIP_TRY(hipHostFree(S->h_sums));
         S->h_sums = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), ((size_t)n + 1) * sizeof(double), hipHostMallocDefault));
-        S->h_sums_cap = (size_t)n + 1;
+        S->h_sums_cap = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), (total + 1) * sizeof(double), hipHostMallocDefault));
+        S->h_sums_cap = total + 1;
     }
-    HIP_TRY(hipMemsetAsync(S->d_sums.p, 0, (size_t)n * sizeof(double), P->stream));
-    const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, n, group, P->stream);
+    return VIPRS_OK;
+}
+
+// Enqueues the reduction of `one` (kernel argument) or of the `n` rows in the sums staging (one H2D copy), n_sums sums per
+// row, then the all-rank reduction and the asynchronous copy into h_sums; sums_collect waits for it.  A rank whose plan
+// holds no SNP contributes zeros to the collective of viprs_state_set_comm.
+static int sums_enqueue(viprs_state* S, bool mixture, int n, int n_sums, const SumsRow* one) {
+    viprs_plan* P = S->plan;
+    HIP_TRY(hipSetDevice(P->device));
+    const size_t total = (size_t)n * n_sums;
+    const SumsRow* h = one ? one : sums_staging(S);
+    int nb = 1;                         // (a row of an empty group has none: its sums are zeros)
+    for (int i = 0; P->m > 0 && i < n; ++i) nb = std::max(nb, h[i].nb);
+    int rc = sums_buffers(S, (size_t)nb * total, total);
     if (rc != VIPRS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipMemcpyAsync(S->h_sums + n, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
+    if (P->m == 0) {
+        HIP_TRY(hipMemsetAsync(S->d_sums.p, 0, total * sizeof(double), P->stream));
+    } else {
+        const SumsRow* rows = one ? nullptr : reinterpret_cast<const SumsRow*>(S->d_sum_rows.p);
+        if (!one) HIP_TRY(hipMemcpyAsync(S->d_sum_rows.p, h, n * sizeof(SumsRow), hipMemcpyHostToDevice, P->stream));
+        const dim3 grid((unsigned)nb, (unsigned)n);
+#define VIPRS_SUMS_ARGS(T)                                                                                                     \
+    *h, rows, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const T*)S->f[VIPRS_FIELD_VAR_MU].p, (const T*)S->f[VIPRS_FIELD_ETA].p, \
+        (const T*)S->f[VIPRS_FIELD_Q].p, (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p, (const T*)S->f[VIPRS_FIELD_STD_BETA].p,       \
+        S->d_var_tau.p
+        if (mixture && S->float_dtype == VIPRS_F32)
+            sums_mixture_kernel<float><<<grid, kSumsBlock, 0, P->stream>>>(S->width, VIPRS_SUMS_ARGS(float), S->d_log_var_tau0.p,
+                                                                           S->d_partials.p);
+        else if (mixture)
+            sums_mixture_kernel<double><<<grid, kSumsBlock, 0, P->stream>>>(S->width, VIPRS_SUMS_ARGS(double),
+                                                                            S->d_log_var_tau0.p, S->d_partials.p);
+        else if (S->float_dtype == VIPRS_F32)
+            sums_kernel<float><<<grid, kSumsBlock, 0, P->stream>>>(VIPRS_SUMS_ARGS(float), S->d_n.p, S->d_weight.p,
+                                                                   S->d_partials.p);
+        else
+            sums_kernel<double><<<grid, kSumsBlock, 0, P->stream>>>(VIPRS_SUMS_ARGS(double), S->d_n.p, S->d_weight.p,
+                                                                    S->d_partials.p);
+#undef VIPRS_SUMS_ARGS
+        HIP_TRY(hipGetLastError());
+        sums_final_kernel<<<dim3((unsigned)n_sums, (unsigned)n), 64, 0, P->stream>>>(S->d_partials.p, nb, n_sums, *h, rows,
+                                                                                     S->d_sums.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (S->comm) {                      // all ranks: ONE all-gather + rank-ordered reduction, still on the plan's stream
+        rc = comm_reduce_on_stream(S->comm, S->d_sums.p, (int)total, n_sums, P->stream);
+        if (rc != VIPRS_OK) return rc;
+    }
+    // pinned host buffer: the copy is truly asynchronous, several plans' sums overlap
+    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, total * sizeof(double), hipMemcpyDeviceToHost, P->stream));
+    HIP_TRY(hipMemcpyAsync(S->h_sums + total, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
+    S->sums_total = total;
     S->sums_pending = true;
     S->sums_empty = false;
     return VIPRS_OK;
 }
 
-template <typename T>
-static int sums_enqueue(viprs_state* S, int64_t off, int64_t vt_off, double one_plus_lambda) {
-    viprs_plan* P = S->plan;
-    const int nb = sums_blocks(P->m);
-    if (S->d_partials.n < (size_t)nb * kNSums) HIP_TRY(S->d_partials.alloc((size_t)nb * kNSums));
-    if (!S->d_sums.p) HIP_TRY(S->d_sums.alloc(kNSums));
-    // pinned landing buffer: kNSums doubles + the plan's device error word (no second synchronisation)
-    if (!S->h_sums) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), (kNSums + 1) * sizeof(double), hipHostMallocDefault));
-        S->h_sums_cap = kNSums + 1;
-    }
-    sums_kernel<T><<<nb, kSumsBlock, 0, P->stream>>>(
-        P->m, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p + off, (const T*)S->f[VIPRS_FIELD_VAR_MU].p + off,
-        (const T*)S->f[VIPRS_FIELD_ETA].p + off, (const T*)S->f[VIPRS_FIELD_Q].p + off,
-        (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p + off, (const T*)S->f[VIPRS_FIELD_STD_BETA].p, S->d_var_tau.p + vt_off,
-        one_plus_lambda, S->d_weight.p, S->d_partials.p);
-    HIP_TRY(hipGetLastError());
-    sums_final_kernel<<<1, 64 * kNSums, 0, P->stream>>>(S->d_partials.p, nb, S->d_sums.p);
-    HIP_TRY(hipGetLastError());
-    if (S->comm) {                      // all ranks: ONE all-gather + rank-ordered reduction, still on the plan's stream
-        const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, kNSums, kNSums, P->stream);
-        if (rc != VIPRS_OK) return rc;
-    }
-    // pinned host buffer: the copy is truly asynchronous, several plans' sums overlap
-    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, kNSums * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipMemcpyAsync(S->h_sums + kNSums, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
-    S->sums_pending = true;
+// a `begin` with nothing to reduce here: an empty rank still takes part in the collective (it contributes zeros),
+// otherwise `end` returns zeros
+static int sums_nothing(viprs_state* S, bool mixture, int n, int n_sums) {
+    if (S->plan->m == 0 && n > 0 && S->comm) return sums_enqueue(S, mixture, n, n_sums, nullptr);
+    S->sums_total = (size_t)n * n_sums;
+    S->sums_pending = false;
+    S->sums_empty = true;
     return VIPRS_OK;
 }
 
-static int sums_finish(viprs_state* S, double* out) {
+// waits for the reduction `begin` enqueued and copies its sums (at most `room` doubles) to `out`
+static int sums_collect(viprs_state* S, double* out, const char* begin, size_t room = SIZE_MAX) {
+    const size_t n = std::min(S->sums_total, room);
+    if (S->sums_empty) {
+        for (size_t k = 0; k < n; ++k) out[k] = 0.0;
+        return VIPRS_OK;
+    }
+    if (!S->sums_pending) return fail(VIPRS_EINVAL, std::string("no device sums in flight (") + begin + ")");
     viprs_plan* P = S->plan;
-    if (!S->sums_pending) return fail(VIPRS_EINVAL, "no device sums in flight (viprs_state_sums_begin)");
+    HIP_TRY(hipSetDevice(P->device));
     HIP_TRY(hipStreamSynchronize(P->stream));
     S->sums_pending = false;
-    for (int k = 0; k < kNSums; ++k) out[k] = S->h_sums[k];
+    for (size_t k = 0; k < n; ++k) out[k] = S->h_sums[k];
     int32_t e = 0;
-    memcpy(&e, S->h_sums + kNSums, sizeof(e));
+    memcpy(&e, S->h_sums + S->sums_total, sizeof(e));
     return e != 0 ? check_device_error(P) : VIPRS_OK;       // slow path only when a hand-off timed out
-}
-
-template <typename T>
-static int sums_launch(viprs_state* S, int64_t off, int64_t vt_off, double one_plus_lambda, double* out) {
-    const int rc = sums_enqueue<T>(S, off, vt_off, one_plus_lambda);
-    return rc != VIPRS_OK ? rc : sums_finish(S, out);
-}
-
-template <typename T>
-static int sums_columns_enqueue(viprs_state* S, int n) {
-    viprs_plan* P = S->plan;
-    const int nb = (int)std::min<int64_t>((P->m + kSumsBlock - 1) / kSumsBlock, 256);
-    const size_t need = (size_t)nb * kNSums * n;
-    if (S->d_partials.n < need) HIP_TRY(S->d_partials.alloc(need));
-    if (S->d_sums.n < (size_t)kNSums * S->width) HIP_TRY(S->d_sums.alloc((size_t)kNSums * S->width));
-    const size_t hcap = (size_t)kNSums * S->width + 1;
-    if (S->h_sums_cap < hcap) {
-        if (S->h_sums) HIP_TRY(hipHostFree(S->h_sums));
-        S->h_sums = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), hcap * sizeof(double), hipHostMallocDefault));
-        S->h_sums_cap = hcap;
-    }
-    sums_kernel<T><<<dim3(nb, n), kSumsBlock, 0, P->stream>>>(
-        P->m, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const T*)S->f[VIPRS_FIELD_VAR_MU].p, (const T*)S->f[VIPRS_FIELD_ETA].p,
-        (const T*)S->f[VIPRS_FIELD_Q].p, (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p, (const T*)S->f[VIPRS_FIELD_STD_BETA].p,
-        S->d_n.p, 0.0, S->d_weight.p, S->d_partials.p, S->d_sumcols.p);
-    HIP_TRY(hipGetLastError());
-    sums_final_kernel<<<n, 64 * kNSums, 0, P->stream>>>(S->d_partials.p, nb, S->d_sums.p);
-    HIP_TRY(hipGetLastError());
-    if (S->comm) {
-        const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, kNSums * n, kNSums, P->stream);
-        if (rc != VIPRS_OK) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, (size_t)kNSums * n * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipMemcpyAsync(S->h_sums + (size_t)kNSums * n, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
-    S->sums_cols = n;
-    S->sums_pending = true;
-    return VIPRS_OK;
 }
 
 extern "C" {
@@ -670,10 +603,6 @@ int viprs_state_synchronize(viprs_state* S) {
     HIP_TRY(hipStreamSynchronize(S->plan->stream));
     return check_device_error(S->plan);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int viprs_state_set_n_per_snp(viprs_state* S, const double* n) {
     if (!S || !n) return fail(VIPRS_EINVAL, "null argument");
@@ -709,19 +638,8 @@ int viprs_state_prep(viprs_state* S, double logit_pi, double log_tau_beta, doubl
     if (P->m == 0) return VIPRS_OK;
     if (!S->d_n.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp has not been called");
     HIP_TRY(hipSetDevice(P->device));
-    const unsigned grid = (unsigned)((P->m + 255) / 256);
-    if (S->float_dtype == VIPRS_F32)
-        prep_kernel<float><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, logit_pi, log_tau_beta, sigma_epsilon, tau_beta,
-                                                        one_plus_lambda, (float*)S->f[VIPRS_FIELD_MU_MULT].p,
-                                                        (float*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                        (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p, S->d_var_tau.p, 0);
-    else
-        prep_kernel<double><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, logit_pi, log_tau_beta, sigma_epsilon, tau_beta,
-                                                         one_plus_lambda, (double*)S->f[VIPRS_FIELD_MU_MULT].p,
-                                                         (double*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                         (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p, S->d_var_tau.p, 0);
-    HIP_TRY(hipGetLastError());
-    return VIPRS_OK;
+    const PrepRow r{0, P->m, 0, logit_pi, log_tau_beta, sigma_epsilon, tau_beta, one_plus_lambda};
+    return prep_launch(S, 1, &r);
 }
 
 int viprs_state_sums(viprs_state* S, double one_plus_lambda, double* out) {
@@ -729,48 +647,38 @@ int viprs_state_sums(viprs_state* S, double one_plus_lambda, double* out) {
     if (S->model_kind != VIPRS_MODEL_SPIKE_SLAB) return fail(VIPRS_EUNSUPPORTED, "device sums: spike-and-slab only");
     viprs_plan* P = S->plan;
     for (int k = 0; k < kNSums; ++k) out[k] = 0.0;
-    if (P->m == 0 && S->comm) {          // an empty rank still takes part in the collective (it contributes zeros)
-        const int rc = sums_enqueue_empty(S, kNSums, kNSums);
-        return rc != VIPRS_OK ? rc : sums_finish(S, out);
-    }
-    if (P->m == 0) return VIPRS_OK;
-    if (!S->d_var_tau.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp / viprs_state_prep have not been called");
-    HIP_TRY(hipSetDevice(P->device));
-    return S->float_dtype == VIPRS_F32 ? sums_launch<float>(S, 0, 0, one_plus_lambda, out)
-                                       : sums_launch<double>(S, 0, 0, one_plus_lambda, out);
+    if (P->m == 0 && !S->comm) return VIPRS_OK;
+    if (P->m > 0 && !S->d_var_tau.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp / viprs_state_prep have not been called");
+    const SumsRow r = sums_row(S, 0, P->m, 0, one_plus_lambda, true, nullptr);
+    const int rc = sums_enqueue(S, false, 1, kNSums, &r);
+    return rc != VIPRS_OK ? rc : sums_collect(S, out, "viprs_state_sums_begin");
 }
 
 int viprs_state_sums_begin(viprs_state* S, double one_plus_lambda) {
     if (!S) return fail(VIPRS_EINVAL, "null argument");
     if (S->model_kind != VIPRS_MODEL_SPIKE_SLAB) return fail(VIPRS_EUNSUPPORTED, "device sums: spike-and-slab only");
     viprs_plan* P = S->plan;
-    if (P->m == 0 && S->comm) return sums_enqueue_empty(S, kNSums, kNSums);
-    if (P->m == 0) { S->sums_pending = false; S->sums_empty = true; return VIPRS_OK; }
-    S->sums_empty = false;
+    if (P->m == 0) return sums_nothing(S, false, 1, kNSums);
     if (!S->d_var_tau.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp / viprs_state_prep have not been called");
-    HIP_TRY(hipSetDevice(P->device));
-    return S->float_dtype == VIPRS_F32 ? sums_enqueue<float>(S, 0, 0, one_plus_lambda)
-                                       : sums_enqueue<double>(S, 0, 0, one_plus_lambda);
+    const SumsRow r = sums_row(S, 0, P->m, 0, one_plus_lambda, true, nullptr);
+    return sums_enqueue(S, false, 1, kNSums, &r);
 }
 
 int viprs_state_sums_end(viprs_state* S, double* out) {
     if (!S || !out) return fail(VIPRS_EINVAL, "null argument");
-    if (S->sums_empty) {
-        for (int k = 0; k < kNSums; ++k) out[k] = 0.0;
-        return VIPRS_OK;
-    }
-    HIP_TRY(hipSetDevice(S->plan->device));
-    return sums_finish(S, out);
+    return sums_collect(S, out, "viprs_state_sums_begin", kNSums);
 }
 
-static void record_col_prep(viprs_state* S, int g, double one_plus_lambda, double sigma_eps, double tau_beta) {
-    if (S->col_prep.size() != (size_t)3 * S->width) S->col_prep.assign((size_t)3 * S->width, NAN);
-    S->col_prep[3 * (size_t)g] = one_plus_lambda;
-    S->col_prep[3 * (size_t)g + 1] = sigma_eps;
-    S->col_prep[3 * (size_t)g + 2] = tau_beta;
+// ---- grid states: one model per column -------------------------------------------------------------------------------
+// (one_plus_lambda, sigma_eps, tau_beta) of a prep, kept for the sums (a grid state keeps no var_tau)
+static void record_prep(double* slot, double one_plus_lambda, double sigma_eps, double tau_beta) {
+    slot[0] = one_plus_lambda;
+    slot[1] = sigma_eps;
+    slot[2] = tau_beta;
 }
-static bool col_prepped(const viprs_state* S, int g) {
-    return S->col_prep.size() == (size_t)3 * S->width && !std::isnan(S->col_prep[3 * (size_t)g]);
+static double* col_last_prep(viprs_state* S, int g) {
+    if (S->col_prep.size() != (size_t)3 * S->width) S->col_prep.assign((size_t)3 * S->width, NAN);
+    return S->col_prep.data() + 3 * (size_t)g;
 }
 
 static int grid_column_check(viprs_state* S, int g) {
@@ -789,23 +697,9 @@ int viprs_state_prep_column(viprs_state* S, int g, double logit_pi, double log_t
     viprs_plan* P = S->plan;
     if (P->m == 0) return VIPRS_OK;
     HIP_TRY(hipSetDevice(P->device));
-    record_col_prep(S, g, one_plus_lambda, sigma_epsilon, tau_beta);
-    const int64_t off = (int64_t)g * P->m;
-    const unsigned grid = (unsigned)((P->m + 255) / 256);
-    if (S->float_dtype == VIPRS_F32)
-        prep_kernel<float><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, logit_pi, log_tau_beta, sigma_epsilon, tau_beta,
-                                                        one_plus_lambda, (float*)S->f[VIPRS_FIELD_MU_MULT].p + off,
-                                                        (float*)S->f[VIPRS_FIELD_U_LOGS].p + off,
-                                                        (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p + off,
-                                                        nullptr, 1);
-    else
-        prep_kernel<double><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, logit_pi, log_tau_beta, sigma_epsilon, tau_beta,
-                                                         one_plus_lambda, (double*)S->f[VIPRS_FIELD_MU_MULT].p + off,
-                                                         (double*)S->f[VIPRS_FIELD_U_LOGS].p + off,
-                                                         (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p + off,
-                                                         nullptr, 1);
-    HIP_TRY(hipGetLastError());
-    return VIPRS_OK;
+    record_prep(col_last_prep(S, g), one_plus_lambda, sigma_epsilon, tau_beta);
+    const PrepRow r{0, P->m, (int64_t)g * P->m, logit_pi, log_tau_beta, sigma_epsilon, tau_beta, one_plus_lambda};
+    return prep_launch(S, 1, &r);
 }
 
 int viprs_state_set_log_var_tau(viprs_state* S, const double* log_var_tau) {
@@ -821,6 +715,19 @@ int viprs_state_set_log_var_tau(viprs_state* S, const double* log_var_tau) {
     return VIPRS_OK;
 }
 
+// a mixture prep row from (log_null_pi, sigma_eps, one_plus_lambda) and the K-vectors logit_pi, log_tau_beta, tau_beta
+static MixPrepRow mix_prep_row(int64_t i0, int64_t i1, int K, const double* scalars, const double* logit_pi,
+                               const double* log_tau_beta, const double* tau_beta) {
+    MixPrepRow r{};
+    r.i0 = i0;
+    r.i1 = i1;
+    r.log_null_pi = scalars[0];
+    r.sigma_eps = scalars[1];
+    r.one_plus_lambda = scalars[2];
+    for (int k = 0; k < K; ++k) { r.logit_pi[k] = logit_pi[k]; r.log_tau[k] = log_tau_beta[k]; r.tau[k] = tau_beta[k]; }
+    return r;
+}
+
 int viprs_state_prep_mixture(viprs_state* S, const double* logit_pi, const double* log_tau_beta, const double* tau_beta,
                              double log_null_pi, double sigma_epsilon, double one_plus_lambda) {
     if (!S || !logit_pi || !log_tau_beta || !tau_beta) return fail(VIPRS_EINVAL, "null argument");
@@ -830,26 +737,9 @@ int viprs_state_prep_mixture(viprs_state* S, const double* logit_pi, const doubl
     viprs_plan* P = S->plan;
     if (P->m == 0) return VIPRS_OK;
     HIP_TRY(hipSetDevice(P->device));
-    const int K = S->width;
-    if (S->d_var_tau.n < (size_t)P->m * K) {
-        HIP_TRY(hipStreamSynchronize(P->stream));
-        HIP_TRY(S->d_var_tau.alloc((size_t)P->m * K));
-    }
-    MixPrepArgs a{};
-    for (int k = 0; k < K; ++k) { a.logit_pi[k] = logit_pi[k]; a.log_tau[k] = log_tau_beta[k]; a.tau[k] = tau_beta[k]; }
-    const unsigned grid = (unsigned)((P->m + 255) / 256);
-    if (S->float_dtype == VIPRS_F32)
-        prep_mixture_kernel<float><<<grid, 256, 0, P->stream>>>(
-            S->d_n.p, P->m, K, a, sigma_epsilon, one_plus_lambda, log_null_pi, (float*)S->f[VIPRS_FIELD_MU_MULT].p,
-            (float*)S->f[VIPRS_FIELD_U_LOGS].p, (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p,
-            (float*)S->f[VIPRS_FIELD_LOG_NULL_PI].p, S->d_var_tau.p);
-    else
-        prep_mixture_kernel<double><<<grid, 256, 0, P->stream>>>(
-            S->d_n.p, P->m, K, a, sigma_epsilon, one_plus_lambda, log_null_pi, (double*)S->f[VIPRS_FIELD_MU_MULT].p,
-            (double*)S->f[VIPRS_FIELD_U_LOGS].p, (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p,
-            (double*)S->f[VIPRS_FIELD_LOG_NULL_PI].p, S->d_var_tau.p);
-    HIP_TRY(hipGetLastError());
-    return VIPRS_OK;
+    const double scalars[3] = {log_null_pi, sigma_epsilon, one_plus_lambda};
+    const MixPrepRow r = mix_prep_row(0, P->m, S->width, scalars, logit_pi, log_tau_beta, tau_beta);
+    return prep_mixture_launch(S, 1, &r);
 }
 
 int viprs_state_sums_mixture_begin(viprs_state* S, double one_plus_lambda) {
@@ -857,63 +747,18 @@ int viprs_state_sums_mixture_begin(viprs_state* S, double one_plus_lambda) {
     if (S->model_kind != VIPRS_MODEL_MIXTURE) return fail(VIPRS_EINVAL, "not a mixture state");
     if (S->width > kMixResidentK) return fail(VIPRS_EUNSUPPORTED, "device-resident mixture iteration: K <= 8");
     viprs_plan* P = S->plan;
-    const int K = S->width, N = kMixSums(K);
-    S->sums_cols = N;
-    if (P->m == 0 && S->comm) return sums_enqueue_empty(S, N, N);
-    if (P->m == 0) { S->sums_pending = false; S->sums_empty = true; return VIPRS_OK; }
-    S->sums_empty = false;
-    if (S->d_var_tau.n < (size_t)P->m * K || !S->d_log_var_tau0.p)
+    const int N = kMixSums(S->width);
+    if (P->m == 0) return sums_nothing(S, true, 1, N);
+    if (S->d_var_tau.n < (size_t)P->m * S->width || !S->d_log_var_tau0.p)
         return fail(VIPRS_EINVAL, "viprs_state_prep_mixture / viprs_state_set_log_var_tau have not been called");
-    HIP_TRY(hipSetDevice(P->device));
-    const int nb = (int)std::min<int64_t>((P->m + kSumsBlock - 1) / kSumsBlock, 1024);
-    if (S->d_partials.n < (size_t)nb * N) HIP_TRY(S->d_partials.alloc((size_t)nb * N));
-    if (S->d_sums.n < (size_t)N) HIP_TRY(S->d_sums.alloc((size_t)N));
-    if (S->h_sums_cap < (size_t)N + 1) {
-        if (S->h_sums) HIP_TRY(hipHostFree(S->h_sums));
-        S->h_sums = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), ((size_t)N + 1) * sizeof(double), hipHostMallocDefault));
-        S->h_sums_cap = (size_t)N + 1;
-    }
-    if (S->float_dtype == VIPRS_F32)
-        sums_mixture_kernel<float><<<nb, kSumsBlock, 0, P->stream>>>(
-            P->m, K, (const float*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const float*)S->f[VIPRS_FIELD_VAR_MU].p,
-            (const float*)S->f[VIPRS_FIELD_ETA].p, (const float*)S->f[VIPRS_FIELD_Q].p, (const float*)S->f[VIPRS_FIELD_ETA_DIFF].p,
-            (const float*)S->f[VIPRS_FIELD_STD_BETA].p, S->d_var_tau.p, S->d_log_var_tau0.p, one_plus_lambda, S->d_partials.p);
-    else
-        sums_mixture_kernel<double><<<nb, kSumsBlock, 0, P->stream>>>(
-            P->m, K, (const double*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const double*)S->f[VIPRS_FIELD_VAR_MU].p,
-            (const double*)S->f[VIPRS_FIELD_ETA].p, (const double*)S->f[VIPRS_FIELD_Q].p, (const double*)S->f[VIPRS_FIELD_ETA_DIFF].p,
-            (const double*)S->f[VIPRS_FIELD_STD_BETA].p, S->d_var_tau.p, S->d_log_var_tau0.p, one_plus_lambda, S->d_partials.p);
-    HIP_TRY(hipGetLastError());
-    sums_final_generic_kernel<<<N, 64, 0, P->stream>>>(S->d_partials.p, nb, N, S->d_sums.p);
-    HIP_TRY(hipGetLastError());
-    if (S->comm) {
-        const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, N, N, P->stream);
-        if (rc != VIPRS_OK) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipMemcpyAsync(S->h_sums + N, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
-    S->sums_pending = true;
-    return VIPRS_OK;
+    const SumsRow r = sums_row(S, 0, P->m, 0, one_plus_lambda, false, nullptr);
+    return sums_enqueue(S, true, 1, N, &r);
 }
 
 int viprs_state_sums_mixture_end(viprs_state* S, double* out) {
     if (!S || !out) return fail(VIPRS_EINVAL, "null argument");
     if (S->model_kind != VIPRS_MODEL_MIXTURE) return fail(VIPRS_EINVAL, "not a mixture state");
-    const int N = kMixSums(S->width);
-    if (S->sums_empty) {
-        for (int k = 0; k < N; ++k) out[k] = 0.0;
-        return VIPRS_OK;
-    }
-    if (!S->sums_pending) return fail(VIPRS_EINVAL, "no device sums in flight (viprs_state_sums_mixture_begin)");
-    viprs_plan* P = S->plan;
-    HIP_TRY(hipSetDevice(P->device));
-    HIP_TRY(hipStreamSynchronize(P->stream));
-    S->sums_pending = false;
-    for (int k = 0; k < N; ++k) out[k] = S->h_sums[k];
-    int32_t e = 0;
-    memcpy(&e, S->h_sums + N, sizeof(e));
-    return e != 0 ? check_device_error(P) : VIPRS_OK;
+    return sums_collect(S, out, "viprs_state_sums_mixture_begin", kMixSums(S->width));
 }
 
 int viprs_state_prep_columns(viprs_state* S, int n, const double* params) {
@@ -927,26 +772,15 @@ int viprs_state_prep_columns(viprs_state* S, int n, const double* params) {
     viprs_plan* P = S->plan;
     if (P->m == 0 || n == 0) return VIPRS_OK;
     HIP_TRY(hipSetDevice(P->device));
-    for (int i = 0; i < n; ++i) record_col_prep(S, (int)params[6 * i], params[6 * i + 5], params[6 * i + 3], params[6 * i + 4]);
-    if (S->d_colparams.n < (size_t)6 * S->width) HIP_TRY(S->d_colparams.alloc((size_t)6 * S->width));
-    if (!S->h_params) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_params), (size_t)11 * S->width * sizeof(double), hipHostMallocDefault));
-    if (!S->ev_prep) HIP_TRY(hipEventCreateWithFlags(&S->ev_prep, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(S->ev_prep));            // the previous launch has read its parameters
-    memcpy(S->h_params, params, (size_t)6 * n * sizeof(double));
-    // pinned staging + copy ON the plan's stream: ordered with the kernel below (the null stream is not)
-    HIP_TRY(hipMemcpyAsync(S->d_colparams.p, S->h_params, (size_t)6 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    const dim3 grid((unsigned)((P->m + 255) / 256), (unsigned)n);
-    if (S->float_dtype == VIPRS_F32)
-        prep_columns_kernel<float><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, S->d_colparams.p,
-                                                                (float*)S->f[VIPRS_FIELD_MU_MULT].p, (float*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                                (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p);
-    else
-        prep_columns_kernel<double><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, S->d_colparams.p,
-                                                                 (double*)S->f[VIPRS_FIELD_MU_MULT].p, (double*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                                 (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S->ev_prep, P->stream));
-    return VIPRS_OK;
+    PrepRow* h = nullptr;
+    const int rc = prep_staging(S, n, &h);
+    if (rc != VIPRS_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        const double* p = params + (size_t)6 * i;
+        record_prep(col_last_prep(S, (int)p[0]), p[5], p[3], p[4]);
+        h[i] = PrepRow{0, P->m, (int64_t)p[0] * P->m, p[1], p[2], p[3], p[4], p[5]};
+    }
+    return prep_launch(S, n, nullptr);
 }
 
 int viprs_state_sums_columns_begin(viprs_state* S, int n, const double* cols) {
@@ -957,46 +791,22 @@ int viprs_state_sums_columns_begin(viprs_state* S, int n, const double* cols) {
         if (cols[2 * i] < 0 || cols[2 * i] >= S->width || cols[2 * i] != floor(cols[2 * i]))
             return fail(VIPRS_EINVAL, "model index out of range");
     viprs_plan* P = S->plan;
-    S->sums_cols = n;
-    if (P->m == 0 && n > 0 && S->comm) return sums_enqueue_empty(S, kNSums * n, kNSums);
-    if (P->m == 0 || n == 0) { S->sums_pending = false; S->sums_empty = true; return VIPRS_OK; }
-    S->sums_empty = false;
+    if (P->m == 0 || n == 0) return sums_nothing(S, false, n, kNSums);
     for (int i = 0; i < n; ++i)
-        if (!col_prepped(S, (int)cols[2 * i])) return fail(VIPRS_EINVAL, "viprs_state_prep_column(s) has not been called");
+        if (std::isnan(*col_last_prep(S, (int)cols[2 * i]))) return fail(VIPRS_EINVAL, "viprs_state_prep_column(s) has not been called");
     HIP_TRY(hipSetDevice(P->device));
-    // (own buffer: the previous reduction that read it has been collected, nothing else does)
-    if (S->d_sumcols.n < (size_t)5 * S->width) HIP_TRY(S->d_sumcols.alloc((size_t)5 * S->width));
-    if (!S->h_params) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_params), (size_t)11 * S->width * sizeof(double), hipHostMallocDefault));
-    // device rows: (column, one_plus_lambda of these sums | what the column's last prep built var_tau from)
-    double* h = S->h_params + (size_t)6 * S->width;
-    for (int i = 0; i < n; ++i) {
-        const int g = (int)cols[2 * i];
-        h[5 * i] = cols[2 * i];
-        h[5 * i + 1] = cols[2 * i + 1];
-        h[5 * i + 2] = S->col_prep[3 * (size_t)g];
-        h[5 * i + 3] = S->col_prep[3 * (size_t)g + 1];
-        h[5 * i + 4] = S->col_prep[3 * (size_t)g + 2];
-    }
-    HIP_TRY(hipMemcpyAsync(S->d_sumcols.p, h, (size_t)5 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    return S->float_dtype == VIPRS_F32 ? sums_columns_enqueue<float>(S, n) : sums_columns_enqueue<double>(S, n);
+    // (the sums staging is free: the previous reduction that read it has been collected)
+    const int rc = row_buffers(S, n);
+    if (rc != VIPRS_OK) return rc;
+    SumsRow* h = sums_staging(S);
+    for (int i = 0; i < n; ++i)
+        h[i] = sums_row(S, 0, P->m, (int64_t)cols[2 * i], cols[2 * i + 1], true, col_last_prep(S, (int)cols[2 * i]));
+    return sums_enqueue(S, false, n, kNSums, nullptr);
 }
 
 int viprs_state_sums_columns_end(viprs_state* S, double* out) {
     if (!S || !out) return fail(VIPRS_EINVAL, "null argument");
-    const int n = S->sums_cols;
-    if (S->sums_empty) {
-        for (int k = 0; k < kNSums * n; ++k) out[k] = 0.0;
-        return VIPRS_OK;
-    }
-    if (!S->sums_pending) return fail(VIPRS_EINVAL, "no device sums in flight (viprs_state_sums_columns_begin)");
-    viprs_plan* P = S->plan;
-    HIP_TRY(hipSetDevice(P->device));
-    HIP_TRY(hipStreamSynchronize(P->stream));
-    S->sums_pending = false;
-    for (int k = 0; k < kNSums * n; ++k) out[k] = S->h_sums[k];
-    int32_t e = 0;
-    memcpy(&e, S->h_sums + (size_t)kNSums * n, sizeof(e));
-    return e != 0 ? check_device_error(P) : VIPRS_OK;
+    return sums_collect(S, out, "viprs_state_sums_columns_begin");
 }
 
 int viprs_state_sums_column(viprs_state* S, int g, double one_plus_lambda, double* out) {
@@ -1005,14 +815,11 @@ int viprs_state_sums_column(viprs_state* S, int g, double one_plus_lambda, doubl
     if (rc != VIPRS_OK) return rc;
     viprs_plan* P = S->plan;
     for (int k = 0; k < kNSums; ++k) out[k] = 0.0;
-    if (P->m == 0 && S->comm) {          // an empty rank still takes part in the collective (it contributes zeros)
-        rc = sums_enqueue_empty(S, kNSums, kNSums);
-        return rc != VIPRS_OK ? rc : sums_finish(S, out);
-    }
-    if (P->m == 0) return VIPRS_OK;
-    const double row[2] = {(double)g, one_plus_lambda};
-    rc = viprs_state_sums_columns_begin(S, 1, row);
-    return rc != VIPRS_OK ? rc : viprs_state_sums_columns_end(S, out);
+    if (P->m == 0 && !S->comm) return VIPRS_OK;
+    if (P->m > 0 && std::isnan(*col_last_prep(S, g))) return fail(VIPRS_EINVAL, "viprs_state_prep_column(s) has not been called");
+    const SumsRow r = sums_row(S, 0, P->m, g, one_plus_lambda, true, col_last_prep(S, g));
+    rc = sums_enqueue(S, false, 1, kNSums, &r);
+    return rc != VIPRS_OK ? rc : sums_collect(S, out, "viprs_state_sums_columns_begin");
 }
 
 int viprs_state_reset_column(viprs_state* S, int g, double pi) {
@@ -1038,13 +845,6 @@ int viprs_state_reset_column(viprs_state* S, int g, double pi) {
     return VIPRS_OK;
 }
 
-
-// doubles per row of the groups' prep parameters (viprs_state_prep_groups / viprs_state_prep_mixture_groups)
-static size_t group_prep_width(const viprs_state* S) {
-    if (S->model_kind == VIPRS_MODEL_GRID) return 7;
-    return S->model_kind == VIPRS_MODEL_MIXTURE ? (size_t)4 + 3 * (size_t)S->width : 6;
-}
-
 // ---- SNP groups: one spike-and-slab (or mixture) model per chromosome, all of them in ONE plan / state (bin/viprs_fit:232-238 fits one
 // model per chromosome unless --genomewide; the chromosomes' LD blocks are independent, so their E-steps share one sweep)
 int viprs_state_set_groups(viprs_state* S, int n_groups, const int64_t* group_start) {
@@ -1052,7 +852,6 @@ int viprs_state_set_groups(viprs_state* S, int n_groups, const int64_t* group_st
     if (S->model_kind == VIPRS_MODEL_MIXTURE && S->width > kMixResidentK)
         return fail(VIPRS_EUNSUPPORTED, "device-resident mixture iteration: K <= 8");
     viprs_plan* P = S->plan;
-    const bool grid = S->model_kind == VIPRS_MODEL_GRID;
     // (a grid state's pair scalars and mask belong to the groups they were given for: dropped once the new list is valid)
     auto drop_pairs = [&]() {
         S->pair_prep.clear();
@@ -1079,19 +878,7 @@ int viprs_state_set_groups(viprs_state* S, int n_groups, const int64_t* group_st
     drop_pairs();
     S->n_groups = n_groups;
     S->group_start.assign(group_start, group_start + n_groups + 1);
-    S->group_max_nb = 1;
-    for (int g = 0; g < n_groups; ++g)
-        S->group_max_nb = std::max(S->group_max_nb, grid ? grid_sums_blocks(group_start[g + 1] - group_start[g])
-                                                          : sums_blocks(group_start[g + 1] - group_start[g]));
-    HIP_TRY(S->d_group_start.alloc((size_t)n_groups + 1));
-    HIP_TRY(hipMemcpy(S->d_group_start.p, group_start, sizeof(int64_t) * ((size_t)n_groups + 1), hipMemcpyHostToDevice));
-    // rows per launch: one per group, or (grid) one per (group, column) pair
-    const size_t pw = group_prep_width(S), sw = grid ? 6 : 2, rows = (size_t)n_groups * (grid ? S->width : 1);
-    HIP_TRY(S->d_group_prep.alloc(pw * rows));
-    HIP_TRY(S->d_group_sumrows.alloc(sw * rows));
-    if (S->h_gparams) { HIP_TRY(hipHostFree(S->h_gparams)); S->h_gparams = nullptr; }
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_gparams), (pw + sw) * rows * sizeof(double), hipHostMallocDefault));
-    if (grid) S->pair_prep.assign((size_t)3 * rows, NAN);
+    if (S->model_kind == VIPRS_MODEL_GRID) S->pair_prep.assign((size_t)3 * n_groups * S->width, NAN);
     return VIPRS_OK;
 }
 
@@ -1106,6 +893,21 @@ static int group_rows_check(const viprs_state* S, int n, const double* rows, int
     return VIPRS_OK;
 }
 
+// the sums of the groups rows[2 i] with one_plus_lambda rows[2 i + 1] (spike-and-slab or mixture: the stored var_tau, no
+// per-SNP weight)
+static int sums_groups_enqueue(viprs_state* S, bool mixture, int n, const double* rows, int n_sums) {
+    HIP_TRY(hipSetDevice(S->plan->device));
+    // (the sums staging is free: the previous reduction that read it has been collected)
+    const int rc = row_buffers(S, n);
+    if (rc != VIPRS_OK) return rc;
+    SumsRow* h = sums_staging(S);
+    for (int i = 0; i < n; ++i) {
+        const size_t g = (size_t)rows[2 * i];
+        h[i] = sums_row(S, S->group_start[g], S->group_start[g + 1], 0, rows[2 * i + 1], false, nullptr);
+    }
+    return sums_enqueue(S, mixture, n, n_sums, nullptr);
+}
+
 int viprs_state_prep_groups(viprs_state* S, int n, const double* params) {
     int rc = group_rows_check(S, n, params, 6);
     if (rc != VIPRS_OK) return rc;
@@ -1114,86 +916,30 @@ int viprs_state_prep_groups(viprs_state* S, int n, const double* params) {
     if (P->m == 0 || n == 0) return VIPRS_OK;
     if (!S->d_n.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp has not been called");
     HIP_TRY(hipSetDevice(P->device));
-    if (!S->ev_prep) HIP_TRY(hipEventCreateWithFlags(&S->ev_prep, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(S->ev_prep));            // the previous launch has read its parameters
-    memcpy(S->h_gparams, params, (size_t)6 * n * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(S->d_group_prep.p, S->h_gparams, (size_t)6 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    int64_t longest = 0;
+    PrepRow* h = nullptr;
+    rc = prep_staging(S, n, &h);
+    if (rc != VIPRS_OK) return rc;
     for (int i = 0; i < n; ++i) {
-        const int g = (int)params[6 * i];
-        longest = std::max(longest, S->group_start[(size_t)g + 1] - S->group_start[(size_t)g]);
+        const double* p = params + (size_t)6 * i;
+        const size_t g = (size_t)p[0];
+        h[i] = PrepRow{S->group_start[g], S->group_start[g + 1], 0, p[1], p[2], p[3], p[4], p[5]};
     }
-    const dim3 grid((unsigned)std::max<int64_t>(1, (longest + 255) / 256), (unsigned)n);
-    if (S->float_dtype == VIPRS_F32)
-        prep_groups_kernel<float><<<grid, 256, 0, P->stream>>>(S->d_n.p, S->d_group_start.p, S->d_group_prep.p,
-                                                               (float*)S->f[VIPRS_FIELD_MU_MULT].p, (float*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                               (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p, S->d_var_tau.p);
-    else
-        prep_groups_kernel<double><<<grid, 256, 0, P->stream>>>(S->d_n.p, S->d_group_start.p, S->d_group_prep.p,
-                                                                (double*)S->f[VIPRS_FIELD_MU_MULT].p, (double*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                                (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p, S->d_var_tau.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S->ev_prep, P->stream));
-    return VIPRS_OK;
+    return prep_launch(S, n, nullptr);
 }
-
-}  // extern "C"
-
-template <typename T>
-static int sums_groups_enqueue(viprs_state* S, int n) {
-    viprs_plan* P = S->plan;
-    const int nb = S->group_max_nb;
-    const size_t need = (size_t)nb * kNSums * n;
-    if (S->d_partials.n < need) HIP_TRY(S->d_partials.alloc(need));
-    if (S->d_sums.n < (size_t)kNSums * S->n_groups) HIP_TRY(S->d_sums.alloc((size_t)kNSums * S->n_groups));
-    const size_t hcap = (size_t)kNSums * S->n_groups + 1;
-    if (S->h_sums_cap < hcap) {
-        if (S->h_sums) HIP_TRY(hipHostFree(S->h_sums));
-        S->h_sums = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), hcap * sizeof(double), hipHostMallocDefault));
-        S->h_sums_cap = hcap;
-    }
-    sums_groups_kernel<T><<<dim3(nb, n), kSumsBlock, 0, P->stream>>>(
-        S->d_group_start.p, S->d_group_sumrows.p, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const T*)S->f[VIPRS_FIELD_VAR_MU].p,
-        (const T*)S->f[VIPRS_FIELD_ETA].p, (const T*)S->f[VIPRS_FIELD_Q].p, (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p,
-        (const T*)S->f[VIPRS_FIELD_STD_BETA].p, S->d_var_tau.p, S->d_partials.p);
-    HIP_TRY(hipGetLastError());
-    sums_final_groups_kernel<<<n, 64 * kNSums, 0, P->stream>>>(S->d_partials.p, nb, S->d_group_start.p, S->d_group_sumrows.p, S->d_sums.p);
-    HIP_TRY(hipGetLastError());
-    if (S->comm) {
-        const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, kNSums * n, kNSums, P->stream);
-        if (rc != VIPRS_OK) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, (size_t)kNSums * n * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipMemcpyAsync(S->h_sums + (size_t)kNSums * n, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
-    S->sums_cols = n;
-    S->sums_pending = true;
-    return VIPRS_OK;
-}
-
-extern "C" {
 
 int viprs_state_sums_groups_begin(viprs_state* S, int n, const double* rows) {
     int rc = group_rows_check(S, n, rows, 2);
     if (rc != VIPRS_OK) return rc;
     if (S->model_kind != VIPRS_MODEL_SPIKE_SLAB) return fail(VIPRS_EINVAL, "not a spike-and-slab state (viprs_state_sums_mixture_groups_begin)");
     viprs_plan* P = S->plan;
-    S->sums_cols = n;
-    if (P->m == 0 && n > 0 && S->comm) return sums_enqueue_empty(S, kNSums * n, kNSums);
-    if (P->m == 0 || n == 0) { S->sums_pending = false; S->sums_empty = true; return VIPRS_OK; }
-    S->sums_empty = false;
+    if (P->m == 0 || n == 0) return sums_nothing(S, false, n, kNSums);
     if (!S->d_var_tau.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp / viprs_state_prep_groups have not been called");
-    HIP_TRY(hipSetDevice(P->device));
-    // (own half of the pinned staging: the previous reduction that read it has been collected)
-    double* h = S->h_gparams + group_prep_width(S) * S->n_groups;
-    memcpy(h, rows, (size_t)2 * n * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(S->d_group_sumrows.p, h, (size_t)2 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    return S->float_dtype == VIPRS_F32 ? sums_groups_enqueue<float>(S, n) : sums_groups_enqueue<double>(S, n);
+    return sums_groups_enqueue(S, false, n, rows, kNSums);
 }
 
 int viprs_state_sums_groups_end(viprs_state* S, double* out) {
     if (S && S->n_groups == 0) return fail(VIPRS_EINVAL, "viprs_state_set_groups has not been called");
-    return viprs_state_sums_columns_end(S, out);          // same landing buffer and bookkeeping: sums_cols rows of VIPRS_N_SUMS
+    return viprs_state_sums_columns_end(S, out);          // same landing buffer and bookkeeping: rows of VIPRS_N_SUMS
 }
 
 // ---- the same for a mixture state (VIPRSMix per chromosome) ----
@@ -1207,71 +953,16 @@ int viprs_state_prep_mixture_groups(viprs_state* S, int n, const double* params)
     if (P->m == 0 || n == 0) return VIPRS_OK;
     if (!S->d_n.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp has not been called");
     HIP_TRY(hipSetDevice(P->device));
-    if (S->d_var_tau.n < (size_t)P->m * K) {
-        HIP_TRY(hipStreamSynchronize(P->stream));
-        HIP_TRY(S->d_var_tau.alloc((size_t)P->m * K));
-    }
-    if (!S->ev_prep) HIP_TRY(hipEventCreateWithFlags(&S->ev_prep, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(S->ev_prep));            // the previous launch has read its parameters
-    memcpy(S->h_gparams, params, (size_t)W * n * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(S->d_group_prep.p, S->h_gparams, (size_t)W * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    int64_t longest = 0;
+    MixPrepRow* h = nullptr;
+    rc = prep_staging(S, n, &h);
+    if (rc != VIPRS_OK) return rc;
     for (int i = 0; i < n; ++i) {
-        const int g = (int)params[(size_t)W * i];
-        longest = std::max(longest, S->group_start[(size_t)g + 1] - S->group_start[(size_t)g]);
+        const double* p = params + (size_t)W * i;
+        const size_t g = (size_t)p[0];
+        h[i] = mix_prep_row(S->group_start[g], S->group_start[g + 1], K, p + 1, p + 4, p + 4 + K, p + 4 + 2 * K);
     }
-    const dim3 grid((unsigned)std::max<int64_t>(1, (longest + 255) / 256), (unsigned)n);
-    if (S->float_dtype == VIPRS_F32)
-        prep_mixture_groups_kernel<float><<<grid, 256, 0, P->stream>>>(
-            S->d_n.p, S->d_group_start.p, K, S->d_group_prep.p, (float*)S->f[VIPRS_FIELD_MU_MULT].p,
-            (float*)S->f[VIPRS_FIELD_U_LOGS].p, (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p,
-            (float*)S->f[VIPRS_FIELD_LOG_NULL_PI].p, S->d_var_tau.p);
-    else
-        prep_mixture_groups_kernel<double><<<grid, 256, 0, P->stream>>>(
-            S->d_n.p, S->d_group_start.p, K, S->d_group_prep.p, (double*)S->f[VIPRS_FIELD_MU_MULT].p,
-            (double*)S->f[VIPRS_FIELD_U_LOGS].p, (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p,
-            (double*)S->f[VIPRS_FIELD_LOG_NULL_PI].p, S->d_var_tau.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S->ev_prep, P->stream));
-    return VIPRS_OK;
+    return prep_mixture_launch(S, n, nullptr);
 }
-
-}  // extern "C"
-
-template <typename T>
-static int sums_mixture_groups_enqueue(viprs_state* S, int n) {
-    viprs_plan* P = S->plan;
-    const int K = S->width, N = kMixSums(K), nb = S->group_max_nb;
-    const size_t need = (size_t)nb * N * n;
-    if (S->d_partials.n < need) HIP_TRY(S->d_partials.alloc(need));
-    if (S->d_sums.n < (size_t)N * S->n_groups) HIP_TRY(S->d_sums.alloc((size_t)N * S->n_groups));
-    const size_t hcap = (size_t)N * S->n_groups + 1;
-    if (S->h_sums_cap < hcap) {
-        if (S->h_sums) HIP_TRY(hipHostFree(S->h_sums));
-        S->h_sums = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), hcap * sizeof(double), hipHostMallocDefault));
-        S->h_sums_cap = hcap;
-    }
-    sums_mixture_groups_kernel<T><<<dim3(nb, n), kSumsBlock, 0, P->stream>>>(
-        S->d_group_start.p, S->d_group_sumrows.p, K, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const T*)S->f[VIPRS_FIELD_VAR_MU].p,
-        (const T*)S->f[VIPRS_FIELD_ETA].p, (const T*)S->f[VIPRS_FIELD_Q].p, (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p,
-        (const T*)S->f[VIPRS_FIELD_STD_BETA].p, S->d_var_tau.p, S->d_log_var_tau0.p, S->d_partials.p);
-    HIP_TRY(hipGetLastError());
-    sums_final_generic_groups_kernel<<<dim3(N, n), 64, 0, P->stream>>>(S->d_partials.p, nb, N, S->d_group_start.p,
-                                                                      S->d_group_sumrows.p, S->d_sums.p);
-    HIP_TRY(hipGetLastError());
-    if (S->comm) {
-        const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, N * n, N, P->stream);
-        if (rc != VIPRS_OK) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipMemcpyAsync(S->h_sums + (size_t)N * n, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
-    S->sums_cols = n;
-    S->sums_pending = true;
-    return VIPRS_OK;
-}
-
-extern "C" {
 
 int viprs_state_sums_mixture_groups_begin(viprs_state* S, int n, const double* rows) {
     if (!S) return fail(VIPRS_EINVAL, "null argument");
@@ -1280,40 +971,18 @@ int viprs_state_sums_mixture_groups_begin(viprs_state* S, int n, const double* r
     if (rc != VIPRS_OK) return rc;
     viprs_plan* P = S->plan;
     const int N = kMixSums(S->width);
-    S->sums_cols = n;
-    if (P->m == 0 && n > 0 && S->comm) return sums_enqueue_empty(S, N * n, N);
-    if (P->m == 0 || n == 0) { S->sums_pending = false; S->sums_empty = true; return VIPRS_OK; }
-    S->sums_empty = false;
+    if (P->m == 0 || n == 0) return sums_nothing(S, true, n, N);
     if (S->d_var_tau.n < (size_t)P->m * S->width || !S->d_log_var_tau0.p)
         return fail(VIPRS_EINVAL, "viprs_state_prep_mixture_groups / viprs_state_set_log_var_tau have not been called");
-    HIP_TRY(hipSetDevice(P->device));
-    double* h = S->h_gparams + group_prep_width(S) * S->n_groups;
-    memcpy(h, rows, (size_t)2 * n * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(S->d_group_sumrows.p, h, (size_t)2 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    return S->float_dtype == VIPRS_F32 ? sums_mixture_groups_enqueue<float>(S, n) : sums_mixture_groups_enqueue<double>(S, n);
+    return sums_groups_enqueue(S, true, n, rows, N);
 }
 
 int viprs_state_sums_mixture_groups_end(viprs_state* S, double* out) {
     if (!S || !out) return fail(VIPRS_EINVAL, "null argument");
     if (S->model_kind != VIPRS_MODEL_MIXTURE) return fail(VIPRS_EINVAL, "not a mixture state");
     if (S->n_groups == 0) return fail(VIPRS_EINVAL, "viprs_state_set_groups has not been called");
-    const size_t total = (size_t)kMixSums(S->width) * S->sums_cols;
-    if (S->sums_empty) {
-        for (size_t k = 0; k < total; ++k) out[k] = 0.0;
-        return VIPRS_OK;
-    }
-    if (!S->sums_pending) return fail(VIPRS_EINVAL, "no device sums in flight (viprs_state_sums_mixture_groups_begin)");
-    viprs_plan* P = S->plan;
-    HIP_TRY(hipSetDevice(P->device));
-    HIP_TRY(hipStreamSynchronize(P->stream));
-    S->sums_pending = false;
-    for (size_t k = 0; k < total; ++k) out[k] = S->h_sums[k];
-    int32_t e = 0;
-    memcpy(&e, S->h_sums + total, sizeof(e));
-    return e != 0 ? check_device_error(P) : VIPRS_OK;
+    return sums_collect(S, out, "viprs_state_sums_mixture_groups_begin");
 }
-
-}  // extern "C"
 
 // ---- SNP groups of a grid state: (group, column) pairs ------------------------------------------------------------------
 static int pair_rows_check(const viprs_state* S, int n, const double* rows, int width) {
@@ -1331,9 +1000,10 @@ static int pair_rows_check(const viprs_state* S, int n, const double* rows, int 
     return VIPRS_OK;
 }
 
-static size_t pair_index(const viprs_state* S, double g, double c) { return (size_t)g * (size_t)S->width + (size_t)c; }
-
-extern "C" {
+// (one_plus_lambda, sigma_eps, tau_beta) of the pair's last prep
+static double* pair_last_prep(viprs_state* S, double g, double c) {
+    return S->pair_prep.data() + 3 * ((size_t)g * (size_t)S->width + (size_t)c);
+}
 
 int viprs_state_prep_grid_groups(viprs_state* S, int n, const double* params) {
     int rc = pair_rows_check(S, n, params, 7);
@@ -1342,106 +1012,44 @@ int viprs_state_prep_grid_groups(viprs_state* S, int n, const double* params) {
     if (P->m == 0 || n == 0) return VIPRS_OK;
     if (!S->d_n.p) return fail(VIPRS_EINVAL, "viprs_state_set_n_per_snp has not been called");
     HIP_TRY(hipSetDevice(P->device));
-    for (int i = 0; i < n; ++i) {                 // what the pair's sums form var_tau from
-        const double* p = params + (size_t)7 * i;
-        const size_t k = 3 * pair_index(S, p[0], p[1]);
-        S->pair_prep[k] = p[6];
-        S->pair_prep[k + 1] = p[4];
-        S->pair_prep[k + 2] = p[5];
-    }
-    if (!S->ev_prep) HIP_TRY(hipEventCreateWithFlags(&S->ev_prep, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(S->ev_prep));            // the previous launch has read its parameters
-    memcpy(S->h_gparams, params, (size_t)7 * n * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(S->d_group_prep.p, S->h_gparams, (size_t)7 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    int64_t longest = 0;
+    PrepRow* h = nullptr;
+    rc = prep_staging(S, n, &h);
+    if (rc != VIPRS_OK) return rc;
     for (int i = 0; i < n; ++i) {
-        const int g = (int)params[(size_t)7 * i];
-        longest = std::max(longest, S->group_start[(size_t)g + 1] - S->group_start[(size_t)g]);
+        const double* p = params + (size_t)7 * i;
+        const size_t g = (size_t)p[0];
+        record_prep(pair_last_prep(S, p[0], p[1]), p[6], p[4], p[5]);
+        h[i] = PrepRow{S->group_start[g], S->group_start[g + 1], (int64_t)p[1] * P->m, p[2], p[3], p[4], p[5], p[6]};
     }
-    const dim3 grid((unsigned)std::max<int64_t>(1, (longest + 255) / 256), (unsigned)n);
-    if (S->float_dtype == VIPRS_F32)
-        prep_grid_groups_kernel<float><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, S->d_group_start.p, S->d_group_prep.p,
-                                                                    (float*)S->f[VIPRS_FIELD_MU_MULT].p, (float*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                                    (float*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p);
-    else
-        prep_grid_groups_kernel<double><<<grid, 256, 0, P->stream>>>(S->d_n.p, P->m, S->d_group_start.p, S->d_group_prep.p,
-                                                                     (double*)S->f[VIPRS_FIELD_MU_MULT].p, (double*)S->f[VIPRS_FIELD_U_LOGS].p,
-                                                                     (double*)S->f[VIPRS_FIELD_SQRT_HALF_VAR_TAU].p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S->ev_prep, P->stream));
-    return VIPRS_OK;
+    return prep_launch(S, n, nullptr);
 }
-
-}  // extern "C"
-
-template <typename T>
-static int sums_grid_groups_enqueue(viprs_state* S, int n) {
-    viprs_plan* P = S->plan;
-    const int nb = S->group_max_nb;
-    const size_t need = (size_t)nb * kNSums * n;
-    if (S->d_partials.n < need) HIP_TRY(S->d_partials.alloc(need));
-    if (S->d_sums.n < (size_t)kNSums * n) HIP_TRY(S->d_sums.alloc((size_t)kNSums * n));
-    const size_t hcap = (size_t)kNSums * n + 1;
-    if (S->h_sums_cap < hcap) {
-        if (S->h_sums) HIP_TRY(hipHostFree(S->h_sums));
-        S->h_sums = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_sums), hcap * sizeof(double), hipHostMallocDefault));
-        S->h_sums_cap = hcap;
-    }
-    sums_grid_groups_kernel<T><<<dim3(nb, n), kSumsBlock, 0, P->stream>>>(
-        P->m, S->d_group_start.p, S->d_group_sumrows.p, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const T*)S->f[VIPRS_FIELD_VAR_MU].p,
-        (const T*)S->f[VIPRS_FIELD_ETA].p, (const T*)S->f[VIPRS_FIELD_Q].p, (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p,
-        (const T*)S->f[VIPRS_FIELD_STD_BETA].p, S->d_n.p, S->d_partials.p);
-    HIP_TRY(hipGetLastError());
-    sums_final_grid_groups_kernel<<<n, 64 * kNSums, 0, P->stream>>>(S->d_partials.p, nb, S->d_group_start.p, S->d_group_sumrows.p,
-                                                                     S->d_sums.p);
-    HIP_TRY(hipGetLastError());
-    if (S->comm) {
-        const int rc = comm_reduce_on_stream(S->comm, S->d_sums.p, kNSums * n, kNSums, P->stream);
-        if (rc != VIPRS_OK) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(S->h_sums, S->d_sums.p, (size_t)kNSums * n * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipMemcpyAsync(S->h_sums + (size_t)kNSums * n, P->d_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, P->stream));
-    S->sums_cols = n;
-    S->sums_pending = true;
-    return VIPRS_OK;
-}
-
-extern "C" {
 
 int viprs_state_sums_grid_groups_begin(viprs_state* S, int n, const double* rows) {
     int rc = pair_rows_check(S, n, rows, 3);
     if (rc != VIPRS_OK) return rc;
     viprs_plan* P = S->plan;
-    S->sums_cols = n;
-    if (P->m == 0 && n > 0 && S->comm) return sums_enqueue_empty(S, kNSums * n, kNSums);
-    if (P->m == 0 || n == 0) { S->sums_pending = false; S->sums_empty = true; return VIPRS_OK; }
-    S->sums_empty = false;
+    if (P->m == 0 || n == 0) return sums_nothing(S, false, n, kNSums);
     for (int i = 0; i < n; ++i)
-        if (std::isnan(S->pair_prep[3 * pair_index(S, rows[(size_t)3 * i], rows[(size_t)3 * i + 1])]))
+        if (std::isnan(*pair_last_prep(S, rows[(size_t)3 * i], rows[(size_t)3 * i + 1])))
             return fail(VIPRS_EINVAL, "viprs_state_prep_grid_groups has not been called for this (group, column) pair");
     HIP_TRY(hipSetDevice(P->device));
-    // device rows (group, column, one_plus_lambda | the pair's last prep); own half of the pinned staging: the previous
-    // reduction that read it has been collected
-    double* h = S->h_gparams + (size_t)7 * S->n_groups * S->width;
+    // (the sums staging is free: the previous reduction that read it has been collected)
+    rc = row_buffers(S, n);
+    if (rc != VIPRS_OK) return rc;
+    SumsRow* h = sums_staging(S);
     for (int i = 0; i < n; ++i) {
-        const size_t k = 3 * pair_index(S, rows[(size_t)3 * i], rows[(size_t)3 * i + 1]);
-        h[6 * i] = rows[(size_t)3 * i];
-        h[6 * i + 1] = rows[(size_t)3 * i + 1];
-        h[6 * i + 2] = rows[(size_t)3 * i + 2];
-        h[6 * i + 3] = S->pair_prep[k];
-        h[6 * i + 4] = S->pair_prep[k + 1];
-        h[6 * i + 5] = S->pair_prep[k + 2];
+        const double* r = rows + (size_t)3 * i;
+        const size_t g = (size_t)r[0];
+        h[i] = sums_row(S, S->group_start[g], S->group_start[g + 1], (int64_t)r[1], r[2], false, pair_last_prep(S, r[0], r[1]));
     }
-    HIP_TRY(hipMemcpyAsync(S->d_group_sumrows.p, h, (size_t)6 * n * sizeof(double), hipMemcpyHostToDevice, P->stream));
-    return S->float_dtype == VIPRS_F32 ? sums_grid_groups_enqueue<float>(S, n) : sums_grid_groups_enqueue<double>(S, n);
+    return sums_enqueue(S, false, n, kNSums, nullptr);
 }
 
 int viprs_state_sums_grid_groups_end(viprs_state* S, double* out) {
     if (!S || !out) return fail(VIPRS_EINVAL, "null argument");
     if (S->model_kind != VIPRS_MODEL_GRID) return fail(VIPRS_EINVAL, "not a grid state");
     if (S->n_groups == 0) return fail(VIPRS_EINVAL, "viprs_state_set_groups has not been called");
-    return viprs_state_sums_columns_end(S, out);          // same landing buffer and bookkeeping: sums_cols rows of VIPRS_N_SUMS
+    return viprs_state_sums_columns_end(S, out);          // same landing buffer and bookkeeping: rows of VIPRS_N_SUMS
 }
 
 int viprs_state_set_group_columns(viprs_state* S, int n_groups, int width, const uint8_t* active) {

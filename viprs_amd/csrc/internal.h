@@ -167,15 +167,10 @@ struct viprs_state {
     viprs::DevBuf<double> d_n, d_var_tau, d_partials, d_sums;   // device-resident EM iteration
     viprs::DevBuf<double> d_weight;                // optional per-SNP weight of sum [0] (several chromosomes in one plan)
     viprs::DevBuf<double> d_log_var_tau0;          // mixture: the log var_tau of the initial state (the reference's ELBO never refreshes it)
-    viprs::DevBuf<double> d_colparams, d_sumcols;  // grid: per-column parameters of the batched prep / of the batched sums
     std::vector<double> col_prep;                  // grid: (one_plus_lambda, sigma_eps, tau_beta) of every column's last prep (3 x width; NaN: none yet)
-    int sums_cols = 0;                      // columns of the reduction in flight (grid: sums_columns_begin; groups: sums_groups_begin)
     // viprs_state_set_groups: contiguous SNP ranges with their own hyper-parameters and their own sums (one model per chromosome)
-    int n_groups = 0, group_max_nb = 0;
+    int n_groups = 0;
     std::vector<int64_t> group_start;              // n_groups + 1 entries
-    viprs::DevBuf<int64_t> d_group_start;
-    viprs::DevBuf<double> d_group_prep, d_group_sumrows;   // per-launch parameter rows (6, mixture: 4 + 3 K / 2 doubles per listed group)
-    double* h_gparams = nullptr;                   // pinned staging of both
     // grid state with groups: one set of hyper-parameters per (group, column) pair
     std::vector<double> pair_prep;                 // (one_plus_lambda, sigma_eps, tau_beta) of every pair's last prep (3 x n_groups x width; NaN: none yet)
     std::vector<uint8_t> group_cols_h;             // viprs_state_set_group_columns: n_groups x width mask (empty: none)
@@ -183,16 +178,21 @@ struct viprs_state {
     viprs::DevBuf<int32_t> d_blk_group;            // group of every block of the plan's dense list (indexed as d_dense)
     uint64_t blk_group_gen = ~0ull;                // the plan's dense_gen d_blk_group was built for
     viprs::DevBuf<int32_t> d_group_lists;          // per launch of 32 active columns and group: its columns under the mask (kGroupListStride ints)
+    // row tables of the batched prep / sums calls (abi_state.hip): room for rows_cap rows each, staged through h_rows
+    // (pinned: rows_cap prep rows, then rows_cap sums rows)
+    viprs::DevBuf<char> d_prep_rows;
+    viprs::DevBuf<char> d_sum_rows;
+    char* h_rows = nullptr;
+    size_t rows_cap = 0;
+    hipEvent_t ev_prep = nullptr;                  // the last batched prep launch (it reads d_prep_rows)
     size_t h_sums_cap = 0;
     double* h_sums = nullptr;               // pinned landing buffer of the device sums
+    size_t sums_total = 0;                  // doubles of the reduction in flight (or of the zeros `end` returns: sums_empty)
     bool sums_pending = false, sums_empty = false;
     viprs_comm* comm = nullptr;             // viprs_state_set_comm: the sums are all-rank sums (one all-gather per reduction)
-    hipEvent_t ev_prep = nullptr;           // the last batched prep launch (it reads d_colparams)
-    double* h_params = nullptr;             // pinned staging of the batched prep (6 x width) / sums (2 x width) parameters
     ~viprs_state() {
         if (h_sums) (void)hipHostFree(h_sums);
-        if (h_params) (void)hipHostFree(h_params);
-        if (h_gparams) (void)hipHostFree(h_gparams);
+        if (h_rows) (void)hipHostFree(h_rows);
         if (ev_prep) (void)hipEventDestroy(ev_prep);
     }
     size_t field_elems(int field) const {

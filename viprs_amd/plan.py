@@ -501,17 +501,25 @@ class DeviceState:
         p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 6)
         L.check(L.lib.viprs_state_prep_groups(self._h, int(p.shape[0]), _ptr(p)))
 
+    def _sums_rows_begin(self, begin, *ids, one_plus_lambda):
+        """Enqueues the sums of the rows (ids[0][i], ..., one_plus_lambda[i]) with the C call `begin`."""
+        n = len(ids[0])
+        r = np.ascontiguousarray(np.column_stack([np.asarray(x, dtype=np.float64) for x in ids] +
+                                                 [np.broadcast_to(np.asarray(one_plus_lambda, dtype=np.float64), (n,))]))
+        self._n_sum_cols = n
+        L.check(begin(self._h, n, _ptr(r)))
+
+    def _sums_rows_end(self, end, n_sums):
+        """(rows, n_sums) sums of the last `_sums_rows_begin`, collected with the C call `end`."""
+        out = np.zeros((self._n_sum_cols, n_sums), dtype=np.float64)
+        L.check(end(self._h, _ptr(out)))
+        return out
+
     def sums_groups_begin(self, groups, one_plus_lambda):
-        r = np.ascontiguousarray(np.column_stack([np.asarray(groups, dtype=np.float64),
-                                                  np.broadcast_to(np.asarray(one_plus_lambda, dtype=np.float64),
-                                                                  (len(groups),))]))
-        self._n_sum_cols = int(r.shape[0])
-        L.check(L.lib.viprs_state_sums_groups_begin(self._h, self._n_sum_cols, _ptr(r)))
+        self._sums_rows_begin(L.lib.viprs_state_sums_groups_begin, groups, one_plus_lambda=one_plus_lambda)
 
     def sums_groups_end(self):
-        out = np.zeros((self._n_sum_cols, L.N_SUMS), dtype=np.float64)
-        L.check(L.lib.viprs_state_sums_groups_end(self._h, _ptr(out)))
-        return out
+        return self._sums_rows_end(L.lib.viprs_state_sums_groups_end, L.N_SUMS)
 
     def prep_mixture_groups(self, params):
         """`prep_mixture` with per-group parameters: rows (group, log_null_pi, sigma_epsilon, one_plus_lambda, logit_pi[K],
@@ -520,17 +528,11 @@ class DeviceState:
         L.check(L.lib.viprs_state_prep_mixture_groups(self._h, int(p.shape[0]), _ptr(p)))
 
     def sums_mixture_groups_begin(self, groups, one_plus_lambda):
-        r = np.ascontiguousarray(np.column_stack([np.asarray(groups, dtype=np.float64),
-                                                  np.broadcast_to(np.asarray(one_plus_lambda, dtype=np.float64),
-                                                                  (len(groups),))]))
-        self._n_sum_cols = int(r.shape[0])
-        L.check(L.lib.viprs_state_sums_mixture_groups_begin(self._h, self._n_sum_cols, _ptr(r)))
+        self._sums_rows_begin(L.lib.viprs_state_sums_mixture_groups_begin, groups, one_plus_lambda=one_plus_lambda)
 
     def sums_mixture_groups_end(self):
         """(n, 7 + 6 K) rows in the layout of `sums_mixture_end`."""
-        out = np.zeros((self._n_sum_cols, 7 + 6 * self.width), dtype=np.float64)
-        L.check(L.lib.viprs_state_sums_mixture_groups_end(self._h, _ptr(out)))
-        return out
+        return self._sums_rows_end(L.lib.viprs_state_sums_mixture_groups_end, 7 + 6 * self.width)
 
     # -- SNP groups of a grid state: one set of hyper-parameters per (group, column) pair ------------
     def prep_grid_groups(self, params):
@@ -541,17 +543,11 @@ class DeviceState:
 
     def sums_grid_groups_begin(self, groups, cols, one_plus_lambda):
         """The sums of the (groups[i], cols[i]) pairs, one launch (asynchronous); `sums_grid_groups_end` collects them."""
-        n = len(groups)
-        r = np.ascontiguousarray(np.column_stack([np.asarray(groups, dtype=np.float64), np.asarray(cols, dtype=np.float64),
-                                                  np.broadcast_to(np.asarray(one_plus_lambda, dtype=np.float64), (n,))]))
-        self._n_sum_cols = n
-        L.check(L.lib.viprs_state_sums_grid_groups_begin(self._h, n, _ptr(r)))
+        self._sums_rows_begin(L.lib.viprs_state_sums_grid_groups_begin, groups, cols, one_plus_lambda=one_plus_lambda)
 
     def sums_grid_groups_end(self):
         """(n, 11) rows in the layout of `sums_columns_end`, [0] the plain sum of gamma over the group."""
-        out = np.zeros((self._n_sum_cols, L.N_SUMS), dtype=np.float64)
-        L.check(L.lib.viprs_state_sums_grid_groups_end(self._h, _ptr(out)))
-        return out
+        return self._sums_rows_end(L.lib.viprs_state_sums_grid_groups_end, L.N_SUMS)
 
     def set_group_columns(self, active):
         """(n_groups, width) boolean mask of the (group, column) pairs the following sweeps update (None clears it):
@@ -602,16 +598,10 @@ class DeviceState:
         L.check(L.lib.viprs_state_prep_columns(self._h, int(p.shape[0]), _ptr(p)))
 
     def sums_columns_begin(self, cols, one_plus_lambda):
-        c = np.ascontiguousarray(np.column_stack([np.asarray(cols, dtype=np.float64),
-                                                  np.broadcast_to(np.asarray(one_plus_lambda, dtype=np.float64),
-                                                                  (len(cols),))]))
-        self._n_sum_cols = int(c.shape[0])
-        L.check(L.lib.viprs_state_sums_columns_begin(self._h, self._n_sum_cols, _ptr(c)))
+        self._sums_rows_begin(L.lib.viprs_state_sums_columns_begin, cols, one_plus_lambda=one_plus_lambda)
 
     def sums_columns_end(self):
-        out = np.zeros((self._n_sum_cols, L.N_SUMS), dtype=np.float64)
-        L.check(L.lib.viprs_state_sums_columns_end(self._h, _ptr(out)))
-        return out
+        return self._sums_rows_end(L.lib.viprs_state_sums_columns_end, L.N_SUMS)
 
     def reset_column(self, g, pi):
         L.check(L.lib.viprs_state_reset_column(self._h, int(g), float(pi)))
