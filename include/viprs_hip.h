@@ -308,6 +308,21 @@ int viprs_state_sums_grid_groups_begin(viprs_state* state, int n, const double* 
 int viprs_state_sums_grid_groups_end(viprs_state* state, double* out);
 int viprs_state_set_group_columns(viprs_state* state, int n_groups, int width, const uint8_t* active);
 
+/* ---- committing SNP groups into grid columns: the pathwise grid search per chromosome ----------------------------------
+ * A chromosome (an SNP group of a spike-and-slab state) whose grid point has stopped stores its state as one column of a grid
+ * state that serves as the result store (never swept; it takes the source's group table).
+ *   viprs_state_commit_groups   `pairs`: n rows of 2 int32 (group, column).  For each row, SNPs [group_start[group],
+ *                               group_start[group+1]) of var_gamma / var_mu / eta / q / eta_diff of `src` are copied into
+ *                               column `column` of the same fields of `dst` (column-major: one contiguous range per field).
+ *                               `src`: a spike-and-slab state with groups set (viprs_state_set_groups); `dst`: a grid state on
+ *                               the same plan with the same float dtype.  ONE kernel launch for every row and field, on the
+ *                               plan's stream behind the work already enqueued (the sweep and sums that produced the state):
+ *                               no stream synchronisation, nothing passes through host memory.  The rows travel through the
+ *                               source's pinned staging of batched prep rows.  Null handles, different plans, different
+ *                               dtypes, wrong model kinds, groups not set, a group or column out of range and n < 0:
+ *                               VIPRS_EINVAL before any launch, `dst` untouched. */
+int viprs_state_commit_groups(viprs_state* dst, const viprs_state* src, int n, const int32_t* pairs);
+
 /* ---- multi-GPU: RCCL over xGMI for the scalar reductions of the EM iteration -------------------------
  * One process per GPU; LD blocks are sharded over the ranks (independent units: within one E-step call
  * the hyper-parameters are fixed and blocks share no q entries, so the data path has NO collective).

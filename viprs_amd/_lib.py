@@ -104,6 +104,7 @@ _PROTOS = {
     "viprs_state_sums_grid_groups_begin": (_i, [_vp, _i, _vp]),
     "viprs_state_sums_grid_groups_end": (_i, [_vp, _vp]),
     "viprs_state_set_group_columns": (_i, [_vp, _i, _i, _vp]),
+    "viprs_state_commit_groups": (_i, [_vp, _vp, _i, _vp]),
     "viprs_comm_unique_id": (_i, [_vp]),
     "viprs_comm_create": (_i, [ctypes.POINTER(_vp), _vp, _i, _i, _i]),
     "viprs_comm_destroy": (_i, [_vp]),

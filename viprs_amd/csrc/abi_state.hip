@@ -1071,3 +1071,107 @@ int viprs_state_set_group_columns(viprs_state* S, int n_groups, int width, const
 }
 
 }  // extern "C"
+
+// ---- committing SNP groups of a spike-and-slab state into columns of a grid state (the pathwise grid search per chromosome:
+// a chromosome whose grid point has stopped stores its state as column `column` of its (m_c, G) result) -------------------
+namespace {
+
+struct CommitRow {
+    int64_t src, dst, len;                         // element offsets into a field of the source / destination state, length
+};
+
+struct CommitFields {
+    const void* src[5];
+    void* dst[5];
+};
+
+// blockIdx.z: the field, blockIdx.y (+ gridDim.y strides): the row, x: the row's elements.  A destination range is split into a
+// scalar head up to the first 16-byte boundary, 16-byte vector stores and a scalar tail; the source is read as 16-byte
+// vectors where it shares the destination's alignment, element by element otherwise.
+template <typename T>
+__global__ __launch_bounds__(256) void commit_groups_kernel(CommitFields f, const CommitRow* __restrict__ rows, int n) {
+    constexpr int V = 16 / sizeof(T);
+    using Vec = typename std::conditional<sizeof(T) == 4, float4, double2>::type;
+    const T* __restrict__ src_f = static_cast<const T*>(f.src[blockIdx.z]);
+    T* __restrict__ dst_f = static_cast<T*>(f.dst[blockIdx.z]);
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int r = blockIdx.y; r < n; r += gridDim.y) {
+        const CommitRow row = rows[r];
+        const T* __restrict__ s = src_f + row.src;
+        T* __restrict__ d = dst_f + row.dst;
+        const int64_t head = std::min<int64_t>(row.len, (V - (int64_t)((reinterpret_cast<uintptr_t>(d) / sizeof(T)) % V)) % V);
+        const int64_t nv = (row.len - head) / V;
+        const int64_t body_end = head + nv * V;
+        const bool aligned = ((reinterpret_cast<uintptr_t>(s + head)) % 16) == 0;
+        for (int64_t u = tid; u < nv; u += stride) {
+            Vec v;
+            if (aligned) {
+                v = *reinterpret_cast<const Vec*>(s + head + u * V);
+            } else {
+                T t[V];
+#pragma unroll
+                for (int k = 0; k < V; ++k) t[k] = s[head + u * V + k];
+                if constexpr (V == 4) v = Vec{t[0], t[1], t[2], t[3]};
+                else v = Vec{t[0], t[1]};
+            }
+            *reinterpret_cast<Vec*>(d + head + u * V) = v;
+        }
+        if (tid < head) d[tid] = s[tid];
+        if (tid < row.len - body_end) d[body_end + tid] = s[body_end + tid];
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int viprs_state_commit_groups(viprs_state* dst, const viprs_state* src, int n, const int32_t* pairs) {
+    if (!dst || !src) return fail(VIPRS_EINVAL, "null state");
+    if (n < 0) return fail(VIPRS_EINVAL, "bad pair count");
+    if (n > 0 && !pairs) return fail(VIPRS_EINVAL, "null argument");
+    if (dst->plan != src->plan) return fail(VIPRS_EINVAL, "the two states are on different plans");
+    if (dst->float_dtype != src->float_dtype) return fail(VIPRS_EINVAL, "the two states have different float dtypes");
+    if (src->model_kind != VIPRS_MODEL_SPIKE_SLAB) return fail(VIPRS_EINVAL, "the source is not a spike-and-slab state");
+    if (dst->model_kind != VIPRS_MODEL_GRID) return fail(VIPRS_EINVAL, "the destination is not a grid state");
+    if (src->n_groups == 0) return fail(VIPRS_EINVAL, "viprs_state_set_groups has not been called on the source");
+    for (int i = 0; i < n; ++i) {
+        if (pairs[2 * i] < 0 || pairs[2 * i] >= src->n_groups) return fail(VIPRS_EINVAL, "group index out of range");
+        if (pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= dst->width) return fail(VIPRS_EINVAL, "column index out of range");
+    }
+    viprs_plan* P = src->plan;
+    if (P->m == 0 || n == 0) return VIPRS_OK;
+    HIP_TRY(hipSetDevice(P->device));
+    // the rows go through the source's pinned staging of batched prep rows (free once its last batched prep has read it)
+    viprs_state* S = const_cast<viprs_state*>(src);
+    CommitRow* h = nullptr;
+    int rc = prep_staging(S, n, &h);
+    if (rc != VIPRS_OK) return rc;
+    static_assert(sizeof(CommitRow) <= sizeof(PrepRow), "a commit row must fit a prep row's room in the staging");
+    int64_t longest = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t g = pairs[2 * i], c = pairs[2 * i + 1];
+        const int64_t i0 = S->group_start[g], i1 = S->group_start[g + 1];
+        h[i] = CommitRow{i0, c * P->m + i0, i1 - i0};
+        longest = std::max(longest, i1 - i0);
+    }
+    HIP_TRY(hipMemcpyAsync(S->d_prep_rows.p, h, (size_t)n * sizeof(CommitRow), hipMemcpyHostToDevice, P->stream));
+    CommitFields f;
+    const int fields[5] = {VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF};
+    for (int k = 0; k < 5; ++k) {
+        f.src[k] = src->f[fields[k]].p;
+        f.dst[k] = dst->f[fields[k]].p;
+    }
+    const int V = 16 / (int)float_size(src->float_dtype);
+    const int64_t units = (longest + V - 1) / V + 1;
+    const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>(1, (units + 255) / 256), 1024),
+                    (unsigned)std::min(n, 65535), 5);
+    const CommitRow* rows = reinterpret_cast<const CommitRow*>(S->d_prep_rows.p);
+    if (src->float_dtype == VIPRS_F32) commit_groups_kernel<float><<<grid, 256, 0, P->stream>>>(f, rows, n);
+    else commit_groups_kernel<double><<<grid, 256, 0, P->stream>>>(f, rows, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S->ev_prep, P->stream));      // (the next batched prep reuses the staging once this copy is done)
+    return VIPRS_OK;
+}
+
+}  // extern "C"

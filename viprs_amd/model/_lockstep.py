@@ -87,6 +87,10 @@ class LockstepEM:
         self.prev_elbo = np.full(G, -np.inf)
         self.prev_sigma_g = np.zeros(G)
         self.plateau_n, self.dropping_n = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)     # ConditionStreak counters
+        # `advance`d to a new grid point and not updated since: a continued fit's fresh ConditionStreak counts nothing on its
+        # first iteration (its last iteration is 0, the fit's first is len(history) + 1 > 1)
+        self.fresh = np.zeros(G, dtype=bool)
+        self.last_sums = np.zeros((G, 11))
         self.elbos = np.zeros(G)
         self.max_eta_diff = np.zeros(G)
         self.last_mse = np.zeros(G)
@@ -106,8 +110,10 @@ class LockstepEM:
 
     def update(self, a, s, i):
         """M-step, ELBO and stopping rules of models `a` on iteration `i` from their sums `s` ((len(a), 11), the layout of
-        `viprs_state_sums`).  Returns the stop code per model (0 = keeps going)."""
+        `viprs_state_sums`); `i`: one iteration number for all, or one per model (aligned with `a`).  Returns the stop code
+        per model (0 = keeps going)."""
         T = self.T
+        i = i if np.ndim(i) == 0 else np.asarray(i)
         fx_pi, fx_tau, fx_sig = self.fx_pi[a], self.fx_tau[a], self.fx_sig[a]
         # ---- VIPRS.m_step, per model (VIPRS.py:426-484) ----
         mean_g = s[:, 0] if self.m_mean is None else s[:, 0] / self.m_mean[a]
@@ -120,17 +126,10 @@ class LockstepEM:
         upd = ~fx_sig
         self.sig[a] = np.where(upd, (1.0 + (-2.0 * s[:, 3]).astype(T)) + self.sigma_g[a], self.sig[a])
         self.sig_is32[a] &= ~upd
-        # ---- ELBO (VIPRS.py:497-581) in the serial fit's dtypes ----
-        sg, sa, ta, pa = self.sigma_g[a], self.sig[a], self.tau[a], self.pi[a]
-        sig32, tau32 = self.sig_is32[a], self.tau_is32[a]
-        e = in_dtype(sa, sig32, lambda v: -np.log(2.0 * np.pi * v))
-        e = np.where(fx_sig, e - in_dtype(sa, sig32, lambda v: 1.0 / v) * (1.0 - 2.0 * s[:, 3] + sg), e - 1.0)
-        e = e * (0.5 * self._per(self.n, a))
-        e = e - (s[:, 5] - np.log(pa) * s[:, 7])
-        e = e - (s[:, 6] - np.log(1.0 - pa) * s[:, 8])
-        e = e + 0.5 * (in_dtype(ta, tau32, lambda v: 1.0 + np.log(v)) * s[:, 7] - s[:, 9])
-        e = e - 0.5 * ta * s[:, 1]
+        sg, sa = self.sigma_g[a], self.sig[a]
+        e = self._elbo(a, s)
         self.elbos[a] = e
+        self.last_sums[a] = s
         self.max_eta_diff[a] = s[:, 10]
         mse = 1.0 - 2.0 * s[:, 3] + (sg - s[:, 1] + s[:, 4])
         self.last_mse[a] = mse
@@ -140,8 +139,10 @@ class LockstepEM:
         prev_e, late = self.prev_elbo[a], i > min_iter
         pl = late & _close(sg, self.prev_sigma_g[a], x_abs_tol) & (s[:, 10] < x_abs_tol * 10)
         dr = (e < prev_e) & ~_close(e, prev_e, 1e3 * f_abs_tol, 1e-4)
-        pn = self.plateau_n[a] = np.where(pl, self.plateau_n[a] + 1, 0)
-        dn = self.dropping_n[a] = np.where(dr, self.dropping_n[a] + 1, 0)
+        counts = ~self.fresh[a]
+        pn = self.plateau_n[a] = np.where(pl & counts, self.plateau_n[a] + 1, 0)
+        dn = self.dropping_n[a] = np.where(dr & counts, self.dropping_n[a] + 1, 0)
+        self.fresh[a] = False
         code = np.zeros(len(a), dtype=np.int64)
         for c, cond in ((8, dn > self.patience), (7, pn > self.patience), (6, late & (s[:, 10] < x_abs_tol)),
                         (5, late & _close(prev_e, e, f_abs_tol)), (4, (h2 > 1.0) | (h2 < 0.0)), (3, sa < 0.0),
@@ -160,6 +161,49 @@ class LockstepEM:
         self.prev_elbo[a[keep]], self.prev_sigma_g[a[keep]] = e[keep], sg[keep]
         return code
 
+    def _elbo(self, a, s):
+        """ELBO (VIPRS.py:497-581) of models `a` over sums `s` with their current hyper-parameters, in the serial fit's
+        dtypes."""
+        fx_sig = self.fx_sig[a]
+        sg, sa, ta, pa = self.sigma_g[a], self.sig[a], self.tau[a], self.pi[a]
+        sig32, tau32 = self.sig_is32[a], self.tau_is32[a]
+        e = in_dtype(sa, sig32, lambda v: -np.log(2.0 * np.pi * v))
+        e = np.where(fx_sig, e - in_dtype(sa, sig32, lambda v: 1.0 / v) * (1.0 - 2.0 * s[:, 3] + sg), e - 1.0)
+        e = e * (0.5 * self._per(self.n, a))
+        e = e - (s[:, 5] - np.log(pa) * s[:, 7])
+        e = e - (s[:, 6] - np.log(1.0 - pa) * s[:, 8])
+        e = e + 0.5 * (in_dtype(ta, tau32, lambda v: 1.0 + np.log(v)) * s[:, 7] - s[:, 9])
+        e = e - 0.5 * ta * s[:, 1]
+        return e
+
+    def advance(self, g, point):
+        """Model g moves on to the grid point `point` (a row of the grid table) from the state and hyper-parameters its last
+        point left: `VIPRSGrid._fit_serial`'s ``set_fixed_params(point)`` followed by ``VIPRS.fit(continued=True)``
+        (VIPRS.py:822-855).  The point's values are fixed in the state precision (fixed sets accumulate; the other
+        hyper-parameters keep their values and dtypes), the model gets a fresh result and fresh stopping streaks, and its
+        starting ELBO -- the new hyper-parameters over the cached sums of the last iteration, as the continued fit's
+        ``_reduce()`` returns them -- goes into the result (not as an iteration) and becomes the previous ELBO.  The caller
+        keeps the finished point's result before.  Returns the starting ELBO."""
+        t = self.T.type
+        if "pi" in point:
+            self.pi[g], self.fx_pi[g] = t(point["pi"]), True
+        if "tau_beta" in point:
+            v = t(point["tau_beta"])
+            self.tau[g], self.tau_is32[g], self.fx_tau[g] = v, _is32(v), True
+        if "sigma_epsilon" in point:
+            v = t(point["sigma_epsilon"])
+            self.sig[g], self.sig_is32[g], self.fx_sig[g] = v, _is32(v), True
+        if "lambda_min" in point:
+            self.lam1[g] = float(1.0 + t(point["lambda_min"]))
+        self.results[g] = OptimizeResult()
+        self.plateau_n[g] = self.dropping_n[g] = 0
+        self.fresh[g] = True
+        self.prev_sigma_g[g] = self.sigma_g[g]
+        e0 = float(self._elbo(np.array([g]), self.last_sums[g][None, :])[0])
+        self.results[g].update(e0, increment=False)
+        self.prev_elbo[g] = e0
+        return e0
+
     def restart(self, g, pi, sigma_epsilon, tau_beta):
         """Model g starts again from (pi, tau_beta) with sigma_epsilon FIXED at the given value (VIPRS.py:1030-1036)."""
         self.pi[g] = pi
@@ -167,9 +211,9 @@ class LockstepEM:
         self.sig[g], self.sig_is32[g] = sigma_epsilon, _is32(sigma_epsilon)
         self.fx_sig[g] = True
 
-    def finish(self):
-        """Models that never stopped: the maximum-iterations record (VIPRS.py:1107-1114)."""
-        for g in range(self.G):
+    def finish(self, models=None):
+        """Models (all, or `models`) that never stopped: the maximum-iterations record (VIPRS.py:1107-1114)."""
+        for g in (range(self.G) if models is None else models):
             if not self.results[g].stop_iteration:
                 self.results[g].update(self.elbos[g], stop_iteration=True, success=False, increment=False,
                                        message=MAX_ITER_MESSAGE)

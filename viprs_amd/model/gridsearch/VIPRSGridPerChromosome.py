@@ -23,6 +23,10 @@ Results are keyed by chromosome, in ``VIPRSGrid``'s per-model layout: ``var_gamm
 post_var_beta [c]`` of shape ``(m_c, G)``; ``pi / tau_beta / sigma_epsilon / _sigma_g / model_elbos [c]`` of length G;
 ``optim_results[c]`` (G results); ``validation_result[c]`` (the chromosome's grid table + ``ELBO``, ``Converged``,
 ``Optimization_message``); ``history[c]["ELBO"][g]`` (the trajectory of pair (c, g)).
+
+The PATHWISE mode (the CLI's default ``--grid-search-mode``: grid point i starts from what point i-1 left) is
+``VIPRSGridPathwisePerChromosome``; both classes share the grid building, the result layout and the summaries
+(``GridPerChromosomeMixin``).
 """
 import copy
 
@@ -36,23 +40,14 @@ from .VIPRSGrid import VIPRSGrid
 _RES = np.finfo(np.float64).resolution
 
 
-class VIPRSGridPerChromosome(PerChromosomeGroups, VIPRSGrid):
+class GridPerChromosomeMixin:
+    """What the per-chromosome grid searches share (mixed in front of the model classes): one grid per chromosome, the
+    per-chromosome result layout of ``VIPRSGrid``, the summaries of one chromosome's models."""
 
-    def __init__(self, gdl, grid, **kwargs):
+    def _set_grids(self, gdl, grid):
         """``grid``: one ``HyperparameterGrid`` -- regenerated per chromosome as the CLI does (``pi`` from the chromosome's
         SNP count, ``lambda_min`` scaled by its LD's ``get_lambda_min``, for grids built from steps) -- or a
         ``{chromosome: HyperparameterGrid}`` dict.  Every chromosome must end up with the same number of grid points."""
-        if np.dtype(kwargs.get("float_precision", "float32")) != np.float32:
-            raise NotImplementedError("VIPRSGridPerChromosome: float32 states only (the grid pair mask has no float64 kernels)")
-        first = next(iter(grid.values())) if isinstance(grid, dict) else grid
-        super().__init__(gdl, grid=first, **kwargs)
-        if self.comm.world_size > 1:
-            raise NotImplementedError("VIPRSGridPerChromosome runs on one GPU (world_size == 1)")
-        if self._e_step_fn is None:
-            from ... import _lib as L
-            if self._plans["*"].info(L.INFO_N_RAGGED) > 0:
-                raise NotImplementedError("VIPRSGridPerChromosome: LD with ragged / banded blocks leaves the dense path, "
-                                          "which the grid pair mask needs")
         lds = gdl.get_ld_matrices()
         self.grids = {}
         for gi, c in enumerate(self.groups):
@@ -74,6 +69,122 @@ class VIPRSGridPerChromosome(PerChromosomeGroups, VIPRSGrid):
         if len(sizes) != 1:
             raise ValueError(f"every chromosome needs the same number of grid points, got {sorted(sizes)}")
         self.n_models = sizes.pop()
+
+    def _publish_chromosomes(self, rec):
+        """The (m_c, G) state arrays (var_gamma / var_mu / q / eta_diff [c], already set) and ``rec[c]`` = dict(var_tau=(m_c, G),
+        theta=[(pi, sigma_epsilon, tau_beta)] * G, sigma_g=(G,), elbo=(G,) in the state precision, results=[G]) in the
+        layout ``VIPRSGrid`` publishes."""
+        T = self._T
+        # (m_c, G) arrays in the layouts VIPRSGrid publishes (C order; eta_diff F order): reductions over them give its bits
+        for name in ("var_gamma", "var_mu", "q"):
+            d = getattr(self, name)
+            for c in d:
+                d[c] = np.ascontiguousarray(d[c])
+        self.eta_diff = {c: np.asfortranarray(v) for c, v in self.eta_diff.items()}
+        self.var_tau, self._log_var_tau = {}, {}
+        self.pi, self.sigma_epsilon, self.tau_beta, self._sigma_g, self.model_elbos = {}, {}, {}, {}, {}
+        self.optim_results, self.validation_result = {}, {}
+        for c in self.groups:
+            r = rec[c]
+            self.var_tau[c] = r["var_tau"]
+            self._log_var_tau[c] = np.log(r["var_tau"])
+            theta = r["theta"]
+            self.pi[c] = np.array([t[0] for t in theta], dtype=T)
+            self.sigma_epsilon[c] = np.array([t[1] for t in theta], dtype=T)
+            self.tau_beta[c] = np.array([t[2] for t in theta], dtype=T)
+            self._sigma_g[c] = np.asarray(r["sigma_g"]).astype(T)
+            elbo = r["elbo"]                                     # (VIPRSGrid keeps the ELBO column in the state precision)
+            self.model_elbos[c] = elbo.astype(f64)
+            self.optim_results[c] = list(r["results"])
+            vr = self.grid_tables[c].copy()
+            vr["ELBO"] = elbo
+            vr["Converged"] = np.array([r.success for r in self.optim_results[c]])
+            vr["Optimization_message"] = [r.message for r in self.optim_results[c]]
+            self.validation_result[c] = vr
+        self.eta = self.compute_eta()
+        self.zeta = self.compute_zeta()
+        self._host_stale = False
+        self.update_posterior_moments()
+        res = self.optim_result
+        res.nit = max(r.nit for rs in self.optim_results.values() for r in rs)
+        res.stop_iteration = True
+        res.success = all(r.success for rs in self.optim_results.values() for r in rs)
+        return self
+
+    # ---- one chromosome's model through the base class's scalar code --------------------------------------------------
+    @property
+    def n_snps(self):
+        """Variants of the model in scope: the whole loader, or one chromosome inside `m_step_of_chromosome`."""
+        return self._chrom_m if getattr(self, "_chrom_m", None) is not None else self.m
+
+    def m_step_of_chromosome(self, c):
+        """`VIPRS.m_step` with nothing fixed over chromosome c's current (1-D) posterior, as the M-step of a model over
+        chromosome c alone computes it (its SNP count, its lambda_min, one chromosome); returns (pi, tau_beta,
+        sigma_epsilon, sigma_g).  (What `bayesian_model_average` runs after averaging a VIPRSGrid.)"""
+        gi = self._gindex[c]
+        keep = ("shapes", "lambda_min", "_n_chroms_total", "fix_params", "_sums", "_sums_valid", "_host_stale", "pi",
+                "tau_beta", "sigma_epsilon", "_sigma_g")
+        saved = {k: getattr(self, k) for k in keep}
+        lam = self._T.type(self._lambda_group[gi])
+        try:
+            self.shapes, self._chrom_m = {c: self.shapes[c]}, int(self._m_group[gi])
+            self.lambda_min = lam if np.isscalar(lam) else self._T.type(0.0)
+            self._n_chroms_total, self.fix_params, self._sums, self._sums_valid, self._host_stale = 1, {}, None, False, False
+            self.pi = self.tau_beta = self.sigma_epsilon = None
+            VIPRS.m_step(self)
+            return self.pi, self.tau_beta, self.sigma_epsilon, self._sigma_g
+        finally:
+            self._chrom_m = None
+            for k, v in saved.items():
+                setattr(self, k, v)
+
+    # ---- summaries ---------------------------------------------------------------------------------------------------
+    def to_validation_table(self, chrom=None):
+        """The validation table of one chromosome, or of all of them with a ``Chromosome`` column."""
+        import pandas as pd
+        if not self.validation_result:
+            raise ValueError("Validation result is not set!")
+        if chrom is not None:
+            return pd.DataFrame(self.validation_result[chrom])
+        return pd.concat([pd.DataFrame(v).assign(Chromosome=c) for c, v in self.validation_result.items()], ignore_index=True)
+
+    def pseudo_validate(self, validation_std_beta=None, chrom=None):
+        """Pseudo-R^2 per grid point of one chromosome's models (``chrom``), or ``{chromosome: values}``."""
+        vb = validation_std_beta if validation_std_beta is not None else getattr(self, "validation_std_beta", None)
+        assert vb is not None, "standardized betas of a validation set are required"
+        chroms = [chrom] if chrom is not None else [c for c in self.groups if c in vb]
+        out = {}
+        for c in chroms:                # (VIPRS.pseudo_validate over a loader that holds chromosome c only, the same operations)
+            cat = lambda d: np.concatenate([np.asarray(d[c])], axis=0)
+            r, b = cat(vb), cat(self.post_mean_beta)
+            rb_w = cat({c: self.q[c] + self.post_mean_beta[c]})
+            rb = np.sum((b.T * r).T, axis=0)
+            out[c] = rb ** 2 / np.sum(b * rb_w, axis=0)
+        return out[chrom] if chrom is not None else out
+
+    def elbo(self, sum_axis=None):
+        return {c: v.copy() for c, v in self.model_elbos.items()}
+
+    objective = elbo
+
+
+class VIPRSGridPerChromosome(GridPerChromosomeMixin, PerChromosomeGroups, VIPRSGrid):
+
+    def __init__(self, gdl, grid, **kwargs):
+        """``grid``: one ``HyperparameterGrid``, regenerated per chromosome, or a ``{chromosome: HyperparameterGrid}`` dict
+        (``GridPerChromosomeMixin._set_grids``)."""
+        if np.dtype(kwargs.get("float_precision", "float32")) != np.float32:
+            raise NotImplementedError("VIPRSGridPerChromosome: float32 states only (the grid pair mask has no float64 kernels)")
+        first = next(iter(grid.values())) if isinstance(grid, dict) else grid
+        super().__init__(gdl, grid=first, **kwargs)
+        if self.comm.world_size > 1:
+            raise NotImplementedError("VIPRSGridPerChromosome runs on one GPU (world_size == 1)")
+        if self._e_step_fn is None:
+            from ... import _lib as L
+            if self._plans["*"].info(L.INFO_N_RAGGED) > 0:
+                raise NotImplementedError("VIPRSGridPerChromosome: LD with ragged / banded blocks leaves the dense path, "
+                                          "which the grid pair mask needs")
+        self._set_grids(gdl, grid)
         self._pair_state = None
 
     def _make_device_state(self, plan):
@@ -224,97 +335,12 @@ class VIPRSGridPerChromosome(PerChromosomeGroups, VIPRSGrid):
                 full = ds.download(name)
                 for c, (a, b) in self._seg.items():
                     getattr(self, name)[c] = full[a:b]
-        # (m_c, G) arrays in the layouts VIPRSGrid publishes (C order; eta_diff F order): reductions over them give its bits
-        for name in ("var_gamma", "var_mu", "q"):
-            d = getattr(self, name)
-            for c in d:
-                d[c] = np.ascontiguousarray(d[c])
-        self.eta_diff = {c: np.asfortranarray(v) for c, v in self.eta_diff.items()}
-        self.var_tau, self._log_var_tau = {}, {}
-        self.pi, self.sigma_epsilon, self.tau_beta, self._sigma_g, self.model_elbos = {}, {}, {}, {}, {}
-        self.optim_results, self.validation_result = {}, {}
+        rec = {}
         for gi, c in enumerate(self.groups):
             ks = gi * G + np.arange(G)
             vt = np.empty((int(self._m_group[gi]), G), dtype=T)
             for g, k in enumerate(ks):                           # what the LAST E-step of the pair was built from
                 vt[:, g] = (self.n_per_snp[c] * (1.0 + th[k]["lam"]) / em.sig_e[k]) + em.tau_e[k]
-            self.var_tau[c] = vt
-            self._log_var_tau[c] = np.log(vt)
-            theta = [em.theta(k) for k in ks]
-            self.pi[c] = np.array([t[0] for t in theta], dtype=T)
-            self.sigma_epsilon[c] = np.array([t[1] for t in theta], dtype=T)
-            self.tau_beta[c] = np.array([t[2] for t in theta], dtype=T)
-            self._sigma_g[c] = em.sigma_g[ks].astype(T)
-            elbo = em.elbos[ks].astype(T)                        # (VIPRSGrid keeps the ELBO column in the state precision)
-            self.model_elbos[c] = elbo.astype(f64)
-            self.optim_results[c] = [em.results[k] for k in ks]
-            vr = self.grid_tables[c].copy()
-            vr["ELBO"] = elbo
-            vr["Converged"] = np.array([r.success for r in self.optim_results[c]])
-            vr["Optimization_message"] = [r.message for r in self.optim_results[c]]
-            self.validation_result[c] = vr
-        self.eta = self.compute_eta()
-        self.zeta = self.compute_zeta()
-        self._host_stale = False
-        self.update_posterior_moments()
-        res = self.optim_result
-        res.nit = max(r.nit for rs in self.optim_results.values() for r in rs)
-        res.stop_iteration = True
-        res.success = all(r.success for rs in self.optim_results.values() for r in rs)
-        return self
-
-    # ---- one chromosome's model through the base class's scalar code --------------------------------------------------
-    @property
-    def n_snps(self):
-        """Variants of the model in scope: the whole loader, or one chromosome inside `m_step_of_chromosome`."""
-        return self._chrom_m if getattr(self, "_chrom_m", None) is not None else self.m
-
-    def m_step_of_chromosome(self, c):
-        """`VIPRS.m_step` with nothing fixed over chromosome c's current (1-D) posterior, as the M-step of a model over
-        chromosome c alone computes it (its SNP count, its lambda_min, one chromosome); returns (pi, tau_beta,
-        sigma_epsilon, sigma_g).  (What `bayesian_model_average` runs after averaging a VIPRSGrid.)"""
-        gi = self._gindex[c]
-        keep = ("shapes", "lambda_min", "_n_chroms_total", "fix_params", "_sums", "_sums_valid", "_host_stale", "pi",
-                "tau_beta", "sigma_epsilon", "_sigma_g")
-        saved = {k: getattr(self, k) for k in keep}
-        lam = self._T.type(self._lambda_group[gi])
-        try:
-            self.shapes, self._chrom_m = {c: self.shapes[c]}, int(self._m_group[gi])
-            self.lambda_min = lam if np.isscalar(lam) else self._T.type(0.0)
-            self._n_chroms_total, self.fix_params, self._sums, self._sums_valid, self._host_stale = 1, {}, None, False, False
-            self.pi = self.tau_beta = self.sigma_epsilon = None
-            VIPRS.m_step(self)
-            return self.pi, self.tau_beta, self.sigma_epsilon, self._sigma_g
-        finally:
-            self._chrom_m = None
-            for k, v in saved.items():
-                setattr(self, k, v)
-
-    # ---- summaries ---------------------------------------------------------------------------------------------------
-    def to_validation_table(self, chrom=None):
-        """The validation table of one chromosome, or of all of them with a ``Chromosome`` column."""
-        import pandas as pd
-        if not self.validation_result:
-            raise ValueError("Validation result is not set!")
-        if chrom is not None:
-            return pd.DataFrame(self.validation_result[chrom])
-        return pd.concat([pd.DataFrame(v).assign(Chromosome=c) for c, v in self.validation_result.items()], ignore_index=True)
-
-    def pseudo_validate(self, validation_std_beta=None, chrom=None):
-        """Pseudo-R^2 per grid point of one chromosome's models (``chrom``), or ``{chromosome: values}``."""
-        vb = validation_std_beta if validation_std_beta is not None else getattr(self, "validation_std_beta", None)
-        assert vb is not None, "standardized betas of a validation set are required"
-        chroms = [chrom] if chrom is not None else [c for c in self.groups if c in vb]
-        out = {}
-        for c in chroms:                # (VIPRS.pseudo_validate over a loader that holds chromosome c only, the same operations)
-            cat = lambda d: np.concatenate([np.asarray(d[c])], axis=0)
-            r, b = cat(vb), cat(self.post_mean_beta)
-            rb_w = cat({c: self.q[c] + self.post_mean_beta[c]})
-            rb = np.sum((b.T * r).T, axis=0)
-            out[c] = rb ** 2 / np.sum(b * rb_w, axis=0)
-        return out[chrom] if chrom is not None else out
-
-    def elbo(self, sum_axis=None):
-        return {c: v.copy() for c, v in self.model_elbos.items()}
-
-    objective = elbo
+            rec[c] = dict(var_tau=vt, theta=[em.theta(k) for k in ks], sigma_g=em.sigma_g[ks], elbo=em.elbos[ks].astype(T),
+                          results=[em.results[k] for k in ks])
+        return self._publish_chromosomes(rec)

@@ -96,7 +96,8 @@ def bayesian_model_average(viprs_grid_model, normalization="softmax"):
     return m
 
 
-# ---- one grid per chromosome (VIPRSGridPerChromosome): the CLI selects or averages per chromosome (bin/viprs_fit:534-551) ----
+# ---- one grid per chromosome (VIPRSGridPerChromosome, VIPRSGridPathwisePerChromosome): the CLI selects or averages per
+# chromosome (bin/viprs_fit:534-551) ----
 def _per_chromosome_result(m):
     from ...utils.optim import OptimizeResult
     res = m.optim_result = OptimizeResult()
@@ -108,10 +109,10 @@ def _per_chromosome_result(m):
 
 
 def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO"):
-    """`select_best_model` per chromosome of a fitted ``VIPRSGridPerChromosome``: every chromosome keeps ITS best grid point,
-    the model ends in ``VIPRSPerChromosome``'s result layout (``pi[c]`` ... scalars, ``pip[c]`` ... of shape (m_c,),
-    ``optim_results[c]`` one result, ``best_model_idx[c]``).  What `select_best_model` picks on each chromosome's own
-    ``VIPRSGrid`` fit, the same arrays."""
+    """`select_best_model` per chromosome of a fitted ``VIPRSGridPerChromosome`` or ``VIPRSGridPathwisePerChromosome``: every
+    chromosome keeps ITS best grid point, the model ends in ``VIPRSPerChromosome``'s result layout (``pi[c]`` ... scalars,
+    ``pip[c]`` ... of shape (m_c,), ``optim_results[c]`` one result, ``best_model_idx[c]``).  What `select_best_model` picks
+    on each chromosome's own ``VIPRSGrid`` fit, the same arrays."""
     if criterion not in ("ELBO", "validation", "pseudo_validation"):
         raise AssertionError(f"unknown criterion {criterion!r}")
     if criterion == "validation":
@@ -149,9 +150,9 @@ def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO
 
 
 def bayesian_model_average_per_chromosome(model, normalization="softmax"):
-    """`bayesian_model_average` per chromosome of a fitted ``VIPRSGridPerChromosome``: the grid points of every chromosome
-    are averaged with weights from THEIR ELBOs and the chromosome's hyper-parameters follow from its averaged posterior
-    (one M-step of that chromosome's model).  ``VIPRSPerChromosome``'s result layout; ``model_weights[c]``."""
+    """`bayesian_model_average` per chromosome of a fitted ``VIPRSGridPerChromosome`` or ``VIPRSGridPathwisePerChromosome``:
+    the grid points of every chromosome are averaged with weights from THEIR ELBOs and the chromosome's hyper-parameters
+    follow from its averaged posterior (one M-step of that chromosome's model).  ``VIPRSPerChromosome``'s result layout; ``model_weights[c]``."""
     m = model
     if m.n_models < 2:
         return m

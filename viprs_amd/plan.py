@@ -560,6 +560,14 @@ class DeviceState:
             raise ValueError(f"active: expected an (n_groups, width) mask, got shape {a.shape}")
         L.check(L.lib.viprs_state_set_group_columns(self._h, int(a.shape[0]), int(a.shape[1]), _ptr(a)))
 
+    def commit_groups(self, src, groups, columns):
+        """Grid state as a result store: SNP group groups[i] of the spike-and-slab state `src` (same plan, same dtype, groups
+        set) is copied into column columns[i] of var_gamma / var_mu / eta / q / eta_diff -- one launch on the plan's stream,
+        no synchronisation."""
+        pairs = np.ascontiguousarray(np.column_stack([np.asarray(groups, dtype=np.int32).ravel(),
+                                                      np.asarray(columns, dtype=np.int32).ravel()]), dtype=np.int32)
+        L.check(L.lib.viprs_state_commit_groups(self._h, src._h, int(pairs.shape[0]), _ptr(pairs)))
+
     # -- one model (column) of a grid state -----------------------------------------------------
     def prep_column(self, g, logit_pi, log_tau_beta, sigma_epsilon, tau_beta, one_plus_lambda):
         L.check(L.lib.viprs_state_prep_column(self._h, int(g), float(logit_pi), float(log_tau_beta),
