@@ -210,7 +210,18 @@ int viprs_state_prep(viprs_state* state, double logit_pi, double log_tau_beta, d
  *   [0] sum gamma  [1] sum zeta  [2] sum(one_plus_lambda zeta + q eta)  [3] sum std_beta eta  [4] sum eta^2
  *   [5] sum g log g  [6] sum (1-g) log(1-g)  [7] sum g  [8] sum (1-g)   (g clipped to [1e-15, 1-1e-15])
  *   [9] sum g log var_tau  [10] max |eta_diff|
- * zeta = gamma (mu^2 + 1/var_tau) in float64 (VIPRS.py:896).  Synchronises the plan's stream.      */
+ * zeta = gamma (mu^2 + 1/var_tau) in float64 (VIPRS.py:896).  Synchronises the plan's stream.
+ * THE ORDER, for every sums call of this header (a "row" is what one output row is summed over: the plan, a grid
+ * column, an SNP group, a (group, column) pair): a row of `len` SNPs takes nb = min(ceil(len / 256), cap) workgroups of
+ * 256 threads, cap = 1024 (spike-and-slab and mixture rows) or 256 (rows of a grid state).  Thread t of workgroup b adds
+ * the terms of SNPs b * 256 + t, + nb * 256, + 2 nb * 256, ... serially (ceil(len / (nb * 256)) additions); the workgroup
+ * combines its 256 accumulators in a binary tree (8 levels; mixture rows: 6 levels within each wave, then the 4 waves in
+ * order); a final pass adds the nb partials, lane l of 64 taking partials l, l + 64, ... serially (ceil(nb / 64)
+ * additions), then a 6-level tree over the lanes.  So the longest path of a row has
+ *   D = ceil(len / (nb * 256)) + 8 (mixture: 9) + ceil(nb / 64) + 6
+ * additions, every sum is within 2^-52 (D + C) sum |terms| of the exact sum of its terms (C: the rounded operations in
+ * one term), and it depends on nothing but the row's own SNPs: not on the other rows of the call, their number or
+ * order, nor on timing.  A row of no SNPs (an empty group) returns zeros.  The maximum [10] ignores NaNs (fmax).        */
 #define VIPRS_N_SUMS 11
 /* Optional per-SNP weights (m doubles; NULL clears them) for sum [0]: with several chromosomes merged into one
  * plan, w_j = 1 / (SNPs of j's chromosome) makes sum [0] the reference's sum of per-chromosome means

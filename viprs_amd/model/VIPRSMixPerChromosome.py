@@ -115,8 +115,14 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
         if c in self.shapes:
             self._init_chromosome_state(c, dict(pi=self.pi, sigma_epsilon=self.sigma_epsilon, tau_beta=self.tau_beta))
         if self._e_step_fn is None:
-            self._push_state()
-            self._upload_log_var_tau()
+            # the device state is the merged one of every chromosome this rank holds (whether or not `c` is among them):
+            # pushed with no model swapped in, so that `chromosomes` lists them all
+            cur, self._cur = self._cur, None
+            try:
+                self._push_state()
+                self._upload_log_var_tau()
+            finally:
+                self._cur = cur
 
     # ---- one lock-step iteration ---------------------------------------------------------------------------------------------
     def _sweep_models(self, a):
