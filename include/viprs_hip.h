@@ -124,7 +124,10 @@ enum viprs_plan_info_key {
     VIPRS_INFO_M = 0, VIPRS_INFO_NNZ = 1, VIPRS_INFO_N_BLOCKS = 2, VIPRS_INFO_N_DENSE = 3,
     VIPRS_INFO_N_RAGGED = 4, VIPRS_INFO_MAX_BLOCK = 5, VIPRS_INFO_LD_BYTES_DEVICE = 6,
     VIPRS_INFO_LD_ELEM_SIZE = 7, VIPRS_INFO_DEVICE = 8, VIPRS_INFO_LOW_MEMORY = 9,
-    VIPRS_INFO_N_CU = 10
+    VIPRS_INFO_N_CU = 10,
+    /* upper form: 1 while the dense blocks hold the upper triangle mirrored into the lower one (the fp32 sweeps' storage),
+     * 0 while the lower triangle is zero (as created; the float64 sweeps' storage) */
+    VIPRS_INFO_UPPER_MIRRORED = 11
 };
 int viprs_plan_info(const viprs_plan* plan, int key, int64_t* value);
 /* Copies the planner's block boundaries (n_blocks + 1 entries) */
@@ -392,6 +395,47 @@ int viprs_plan_timing_history(viprs_plan* plan, int which, double* ms, int capac
 int viprs_plan_last_math_modes(const viprs_plan* plan, int* mask);
 /* Number of SNPs of the last sweep that took the skip branch (e_step.hpp:410-413).            */
 int viprs_plan_last_skipped(viprs_plan* plan, int64_t* n_skipped);
+
+/* ---- LD product: Y = R B over EVERY block of a plan -------------------------------------------------------------------
+ * What the reference computes with `ld.dot(B)`: the pseudo-validation metrics against a validation LD panel
+ * (viprs/eval/pseudo_metrics.py:122-127: R_val B for all grid models at once) and q + beta = R beta for effects that were
+ * not fitted in this process (BayesPRSModel.py:397-404).  `B` and `Y` are (m, n_cols), column-major like the grid arrays
+ * (n_cols = 1: plain vectors), in the state precision `float_dtype`.
+ *   S[j, g] = sum over the OFF-DIAGONAL entries (j, i) of row j of the symmetric matrix the plan stands for of r_ji B[i, g]
+ *             (symmetric form: the stored diagonal entry is skipped; upper form: the stored row (j, j + len_j] and the
+ *             transposed entries (i, j) of the rows i < j that reach j -- the R of q = (R - I) eta, e_step.hpp:410-428);
+ *             integer LD: r_ji is the stored integer
+ *   Y = fl(fl(dq_scale) * S)            include_diagonal == 0   (the q of a given eta)
+ *   Y = fl(fl(fl(dq_scale) * S) + B)    include_diagonal != 0   (unit diagonal: R B)
+ * dq_scale is rounded to the state precision first; the multiply and the add are two separately rounded operations.
+ * viprs_plan_set_active_blocks does NOT filter the product.  No floating-point atomics.
+ * THE ORDER.  The entries of row j lie in a window of W consecutive columns starting at c_lo: a dense block's rows take
+ * the block (W = its size); a windowed row of the symmetric form its stored window; of the upper form the columns from the
+ * lowest row that reaches j to j + len_j.  W = L + 1 for a row of L off-diagonal entries whose window has no gaps (always,
+ * for dense blocks and for symmetric windows).  With V = 16 / sizeof(LD element) (4 for fp32 LD, 8 for int16, 16 for int8),
+ * the entry at column c_lo + e goes to accumulator e % V of lane (e / V) % 64; a lane adds its entries in ascending e,
+ * each by one fused multiply-add in the state precision (float32 state: fp32; float64 state: float64; the LD element is
+ * converted to the state precision first, exactly for int8 / int16 / fp32 LD); the diagonal and columns without an entry
+ * add an exact zero.  A lane's V accumulators are then summed in a binary tree, then the 64 lanes in a binary tree.  The
+ * longest path of a row therefore has
+ *   D(L) = ceil((L + 1) / (64 V)) + log2(V) + 6   additions     (W in place of L + 1 for a window with gaps),
+ * every S is within eps_T * D(L) * sum |r_ji B[i, g]| of the exact sum, and it depends on nothing but the row's entries
+ * and column g of B: not on the other columns or their number, not on which storage of the upper form the dense blocks are
+ * in, not on the active blocks, not on timing.  Two calls give identical bits.
+ *   viprs_plan_dot          host buffers in and out, on the plan's stream, synchronous
+ *   viprs_state_dot         B = a resident field of `state`: VIPRS_FIELD_ETA only ((m,) for spike-and-slab and mixture
+ *                           states, (m, G) for grid states); `y_host` receives m x n_cols results, no input is moved
+ *   viprs_plan_last_dot_ms  HIP-event time of the kernels of the last product on this plan; the sweeps' timing ring
+ *                           (viprs_plan_last_kernel_ms, viprs_plan_timing_history) never sees a product
+ * Bad dtype code, n_cols < 1, a field other than VIPRS_FIELD_ETA, null pointers: VIPRS_EINVAL before any launch, `y_host`
+ * untouched.  An empty plan returns VIPRS_OK.  Upper form: the product reads the dense blocks in whichever storage the last
+ * sweep left them (the fp32 sweeps' mirrored squares as whole rows; the float64 sweeps' zero lower triangle by gathering
+ * the entries left of the diagonal from the column above it), so a product between EM rounds converts nothing; only a plan
+ * that has not been swept yet is mirrored once. */
+int viprs_plan_dot(viprs_plan* plan, int float_dtype, int n_cols, const void* b_host, void* y_host,
+                   double dq_scale, int include_diagonal);
+int viprs_state_dot(viprs_state* state, int field, double dq_scale, int include_diagonal, void* y_host);
+int viprs_plan_last_dot_ms(viprs_plan* plan, double* ms);
 
 /* ---- measurement support: synthetic LD generated on the device (bench.py, tests) --------------
  * The "longrange" LD blocks of viprs_amd/utils/synthetic.py (the workload of BASELINE.json's configs, SURVEY.md 8d: the

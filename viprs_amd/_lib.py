@@ -21,7 +21,7 @@ MODEL_SPIKE_SLAB, MODEL_MIXTURE, MODEL_GRID = 0, 1, 2
 (FIELD_STD_BETA, FIELD_U_LOGS, FIELD_SQRT_HALF_VAR_TAU, FIELD_MU_MULT, FIELD_LOG_NULL_PI,
  FIELD_VAR_GAMMA, FIELD_VAR_MU, FIELD_ETA, FIELD_Q, FIELD_ETA_DIFF) = range(10)
 (INFO_M, INFO_NNZ, INFO_N_BLOCKS, INFO_N_DENSE, INFO_N_RAGGED, INFO_MAX_BLOCK, INFO_LD_BYTES_DEVICE,
- INFO_LD_ELEM_SIZE, INFO_DEVICE, INFO_LOW_MEMORY, INFO_N_CU) = range(11)
+ INFO_LD_ELEM_SIZE, INFO_DEVICE, INFO_LOW_MEMORY, INFO_N_CU, INFO_UPPER_MIRRORED) = range(12)
 
 OK, EINVAL, ELAYOUT, EDEVICE, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 N_SUMS = 11
@@ -121,6 +121,9 @@ _PROTOS = {
     "viprs_plan_last_math_modes": (_i, [_vp, ctypes.POINTER(_i)]),
     "viprs_plan_timing_reset": (_i, [_vp]),
     "viprs_plan_timing_history": (_i, [_vp, _i, ctypes.POINTER(_d), _i, ctypes.POINTER(_i)]),
+    "viprs_plan_dot": (_i, [_vp, _i, _i, _vp, _vp, _d, _i]),
+    "viprs_state_dot": (_i, [_vp, _i, _d, _i, _vp]),
+    "viprs_plan_last_dot_ms": (_i, [_vp, ctypes.POINTER(_d)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

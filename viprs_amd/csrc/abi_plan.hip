@@ -132,6 +132,7 @@ viprs_plan::~viprs_plan() {
     viprs::team_launch_forget(this);           // (a later plan may get this address or this stream handle)
     delete scratch;
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_dot) if (e) (void)hipEventDestroy(e);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
     if (side_stream) (void)hipStreamDestroy(side_stream);
@@ -402,6 +403,9 @@ namespace viprs {
 // conversion runs on the plan's stream, once per change of kernel family (a fit keeps to one).
 int ensure_upper_storage(viprs_plan* P, bool mirrored) {
     // (every dense block of the plan, whatever subset the sweeps currently visit: the flag is per plan)
+    // what the last launcher asked for, noted for every plan before the early return (only upper-form plans ever read it:
+    // the LD product mirrors a plan that nobody wanted with a zero lower triangle, abi_dot.hip)
+    P->unmirrored_wanted = !mirrored;
     if (!P->low_memory || P->dense_all_h.empty() || (P->mirror != 0) == mirrored) return VIPRS_OK;
     int max_np = 0;
     for (const BlockDesc& d : P->dense_all_h) max_np = std::max(max_np, (d.size + kPanel - 1) / kPanel);
@@ -617,6 +621,7 @@ int viprs_plan_info(const viprs_plan* P, int key, int64_t* value) {
         case VIPRS_INFO_DEVICE: *value = P->device; break;
         case VIPRS_INFO_LOW_MEMORY: *value = P->low_memory; break;
         case VIPRS_INFO_N_CU: *value = P->n_cu; break;
+        case VIPRS_INFO_UPPER_MIRRORED: *value = P->mirror; break;
         default: return fail(VIPRS_EINVAL, "unknown info key");
     }
     return VIPRS_OK;

@@ -151,6 +151,17 @@ struct viprs_plan {
     // launch (record_start_event): with an empty stream the event is reached at once, and whatever the host does between the
     // record and the launch -- occupancy query, team split, launch gate, a scheduler hiccup -- would count as kernel time
     hipEvent_t pending_start_event = nullptr;
+    // LD product (abi_dot.hip, ld_dot.h): its own tables over EVERY block of the plan (the product is not filtered by
+    // viprs_plan_set_active_blocks), built by the first product; its own event pair (the sweeps' timing ring never sees it)
+    bool dot_built = false;
+    viprs::DevBuf<viprs::BlockDesc> d_dot_blocks;  // dense_all_h, then ragged_all_h
+    // work lists in the order of the plan's full block lists: (block of d_dot_blocks) << 32 | (first) row of the block; dense [k]: 1 << k rows per item
+    viprs::DevBuf<int64_t> d_dot_rows_dense[3], d_dot_rows_ragged;
+    viprs::DevBuf<int32_t> d_dot_first;            // upper form with windowed blocks: the first row whose entries reach row j
+    viprs::DevBuf<char> d_dot_b, d_dot_y;          // staging of the host-buffer call / the results
+    hipEvent_t ev_dot[2] = {nullptr, nullptr};
+    bool dot_timed = false;
+    bool unmirrored_wanted = false;                // the last launch that asked for a storage of the upper form wanted the zero lower triangle
 
     ~viprs_plan();
 };
@@ -250,5 +261,8 @@ template <typename U> int launch_band(viprs_plan* P, EStepArgs<float> A, int mod
 int band_ring_panels(const viprs_plan* P);
 // batched grid E-step on the matrix cores
 template <typename U> int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A);
+// LD product Y = dq_scale (R - diag) B (+ B) over every block of the plan (ld_dot.h); device pointers, (m, n_cols) column-major
+template <typename U> int launch_ld_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale,
+                                        int include_diagonal);
 
 }  // namespace viprs

@@ -1,0 +1,3 @@
+#define DOT_U int8_t
+#define DOT_DENSE 1
+#include "launch_ld_dot.inc"

@@ -43,6 +43,29 @@ def _is_numeric(x):
     return isinstance(x, (int, float, np.number, np.ndarray))
 
 
+def _pseudo_r2_external(validation_ld, std_beta, beta, device=0):
+    """`viprs_amd.eval.pseudo_r2` of `beta` against an external panel: plans are made from ``(left_bound, indptr, data,
+    low_memory)`` tuples and closed again, plans that are handed in stay open."""
+    from ..eval.pseudo_metrics import pseudo_r2
+    from ..plan import LDPlan
+    plans, own = {}, []
+    try:
+        for c in beta:
+            if c not in validation_ld:
+                raise ValueError(f"validation_ld has no LD for chromosome {c}")
+            ld = validation_ld[c]
+            if isinstance(ld, (tuple, list)):
+                lb, ip, data, low_memory = ld
+                ld = LDPlan(np.ascontiguousarray(lb, dtype=np.int32), np.ascontiguousarray(ip), np.ascontiguousarray(data),
+                            bool(low_memory), device=device)
+                own.append(ld)
+            plans[c] = ld
+        return pseudo_r2(plans, std_beta, beta)
+    finally:
+        for ld in own:
+            ld.close()
+
+
 class VIPRS:
 
     _always_merge = False        # subclasses that need the one-plan layout even for a single local chromosome
@@ -565,15 +588,27 @@ class VIPRS:
             tables[c] = pd.concat([tables[c], pd.DataFrame(add, index=tables[c].index)], axis=1)
         return tables if per_chromosome else pd.concat([tables[c] for c in chroms])
 
-    def pseudo_validate(self, validation_std_beta=None):
+    def pseudo_validate(self, validation_std_beta=None, validation_ld=None):
         """Pseudo-R^2 of the fitted effects against standardized marginal betas of an independent
-        cohort that shares this LD reference: (r'b)^2 / (b'Rb) with R b = q + b
-        (BayesPRSModel.py:397-410, pseudo_metrics.py `_streamlined_pseudo_r2`); one value per model
-        for grid fits."""
+        cohort: (r'b)^2 / (b'Rb), one value per model for grid fits.
+
+        ``validation_ld=None``: the cohort shares this LD reference, R b = q + b of the fit
+        (BayesPRSModel.py:397-410, pseudo_metrics.py `_streamlined_pseudo_r2`).
+
+        ``validation_ld``: the LD of an external validation panel, ``{chromosome: LDPlan}`` or
+        ``{chromosome: (left_bound, indptr, data, low_memory)}`` (plans are made from the tuples and closed again):
+        R_val b is the device LD product of every model's effects in one pass (`viprs_amd.eval.pseudo_r2`,
+        pseudo_metrics.py:52-70, 98-127).  The panel's SNPs are taken as matched to the model's.  Several ranks:
+        NotImplementedError (the product is not sharded)."""
         vb = validation_std_beta if validation_std_beta is not None else getattr(self, "validation_std_beta", None)
         assert self.post_mean_beta is not None, "The posterior means for BETA are not set. Call `.fit()` first."
         assert vb is not None, "standardized betas of a validation set are required"
         chroms = sorted(self.post_mean_beta)
+        if validation_ld is not None:
+            if self.comm.world_size > 1:
+                raise NotImplementedError("pseudo_validate(validation_ld=...) runs on one rank only")
+            return _pseudo_r2_external(validation_ld, vb, {c: self.post_mean_beta[c] for c in chroms},
+                                       device=getattr(self, "device", 0))
         q = self.q_full if self.comm.world_size > 1 else self.q       # several ranks: gathered at the end of fit()
         cat = lambda d: np.concatenate([np.asarray(d[c]) for c in chroms], axis=0)
         r, b = cat(vb), cat(self.post_mean_beta)

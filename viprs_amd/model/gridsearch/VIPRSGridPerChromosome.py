@@ -148,13 +148,21 @@ class GridPerChromosomeMixin:
             return pd.DataFrame(self.validation_result[chrom])
         return pd.concat([pd.DataFrame(v).assign(Chromosome=c) for c, v in self.validation_result.items()], ignore_index=True)
 
-    def pseudo_validate(self, validation_std_beta=None, chrom=None):
-        """Pseudo-R^2 per grid point of one chromosome's models (``chrom``), or ``{chromosome: values}``."""
+    def pseudo_validate(self, validation_std_beta=None, chrom=None, validation_ld=None):
+        """Pseudo-R^2 per grid point of one chromosome's models (``chrom``), or ``{chromosome: values}``.  `validation_ld`:
+        the LD of an external validation panel per chromosome, as `VIPRS.pseudo_validate` takes it (one rank only)."""
         vb = validation_std_beta if validation_std_beta is not None else getattr(self, "validation_std_beta", None)
         assert vb is not None, "standardized betas of a validation set are required"
         chroms = [chrom] if chrom is not None else [c for c in self.groups if c in vb]
         out = {}
         for c in chroms:                # (VIPRS.pseudo_validate over a loader that holds chromosome c only, the same operations)
+            if validation_ld is not None:
+                if self.comm.world_size > 1:
+                    raise NotImplementedError("pseudo_validate(validation_ld=...) runs on one rank only")
+                from ..VIPRS import _pseudo_r2_external
+                out[c] = _pseudo_r2_external({c: validation_ld[c]}, {c: vb[c]}, {c: self.post_mean_beta[c]},
+                                              device=getattr(self, "device", 0))
+                continue
             cat = lambda d: np.concatenate([np.asarray(d[c])], axis=0)
             r, b = cat(vb), cat(self.post_mean_beta)
             rb_w = cat({c: self.q[c] + self.post_mean_beta[c]})

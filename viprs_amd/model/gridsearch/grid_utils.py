@@ -12,10 +12,12 @@ import copy
 import numpy as np
 
 
-def select_best_model(viprs_grid_model, validation_gdl=None, criterion="ELBO"):
+def select_best_model(viprs_grid_model, validation_gdl=None, criterion="ELBO", validation_ld=None):
     """grid_utils.py:8-100.  `pseudo_validation`: the model with the highest summary-statistics pseudo-R^2 on
     held-out standardized betas -- `validation_gdl` may be a `{chromosome: std_beta}` dict (or an object with
-    that dict as `.std_beta`); otherwise `viprs_grid_model.validation_std_beta` is used."""
+    that dict as `.std_beta`); otherwise `viprs_grid_model.validation_std_beta` is used.  `validation_ld` (a
+    `{chromosome: LDPlan}` dict, or of `(left_bound, indptr, data, low_memory)` tuples) scores the models against the LD of
+    an external validation panel instead of the training LD (`VIPRS.pseudo_validate`)."""
     if criterion not in ("ELBO", "validation", "pseudo_validation"):
         raise AssertionError(f"unknown criterion {criterion!r}")
     if criterion == "validation":
@@ -33,7 +35,8 @@ def select_best_model(viprs_grid_model, validation_gdl=None, criterion="ELBO"):
         if vb is None:
             raise ValueError("Validation GWADataLoader or standardized betas from a validation set must be "
                              "initialized for the pseudo_validation criterion.")
-        score = np.nan_to_num(np.asarray(m.pseudo_validate(vb), dtype=np.float64), nan=0.0, neginf=0.0, posinf=0.0)
+        score = np.nan_to_num(np.asarray(m.pseudo_validate(vb) if validation_ld is None else
+                                         m.pseudo_validate(vb, validation_ld=validation_ld), dtype=np.float64), nan=0.0, neginf=0.0, posinf=0.0)
         m.validation_result["Pseudo_Validation_R2"] = score
     score = score.copy()
     score[~ok] = -np.inf
@@ -108,11 +111,11 @@ def _per_chromosome_result(m):
     return m
 
 
-def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO"):
+def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO", validation_ld=None):
     """`select_best_model` per chromosome of a fitted ``VIPRSGridPerChromosome`` or ``VIPRSGridPathwisePerChromosome``: every
     chromosome keeps ITS best grid point, the model ends in ``VIPRSPerChromosome``'s result layout (``pi[c]`` ... scalars,
     ``pip[c]`` ... of shape (m_c,), ``optim_results[c]`` one result, ``best_model_idx[c]``).  What `select_best_model` picks
-    on each chromosome's own ``VIPRSGrid`` fit, the same arrays."""
+    on each chromosome's own ``VIPRSGrid`` fit, the same arrays.  `validation_ld`: as in `select_best_model`."""
     if criterion not in ("ELBO", "validation", "pseudo_validation"):
         raise AssertionError(f"unknown criterion {criterion!r}")
     if criterion == "validation":
@@ -132,7 +135,8 @@ def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO
             if vb is None:
                 raise ValueError("Validation GWADataLoader or standardized betas from a validation set must be "
                                  "initialized for the pseudo_validation criterion.")
-            score = np.nan_to_num(np.asarray(m.pseudo_validate(vb, chrom=c), dtype=np.float64), nan=0.0, neginf=0.0, posinf=0.0)
+            score = np.nan_to_num(np.asarray(m.pseudo_validate(vb, chrom=c) if validation_ld is None else
+                                             m.pseudo_validate(vb, chrom=c, validation_ld=validation_ld), dtype=np.float64), nan=0.0, neginf=0.0, posinf=0.0)
             m.validation_result[c]["Pseudo_Validation_R2"] = score
         score = score.copy()
         score[~ok] = -np.inf

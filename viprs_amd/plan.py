@@ -229,6 +229,32 @@ class LDPlan:
         L.check(L.lib.viprs_plan_last_skipped(self.handle, ctypes.byref(n)))
         return n.value
 
+    # -- LD product ---------------------------------------------------------------------------
+    def dot(self, B, dq_scale=1.0, include_diagonal=True):
+        """``R @ B`` over every block of the plan (`viprs_plan_dot`; the reference's ``ld.dot(B)``): `B` is ``(m,)`` or
+        ``(m, G)``, float32 or float64, in either memory order; the result has the caller's shape and dtype.  `R` has a
+        unit diagonal and off-diagonal entries ``dq_scale * stored``; ``include_diagonal=False`` leaves the diagonal out
+        (the ``q`` of a given ``eta``).  `set_active_blocks` does not filter the product."""
+        B = np.asarray(B)
+        if B.dtype not in _FLOAT_CODE:
+            raise ValueError(f"Buffer dtype mismatch for B: expected float32 or float64, got {B.dtype}")
+        if B.ndim not in (1, 2) or B.shape[0] != self.m or (B.ndim == 2 and B.shape[1] < 1):
+            raise ValueError(f"B: expected shape ({self.m},) or ({self.m}, G), got {B.shape}")
+        b = np.asfortranarray(B)
+        y = np.empty(b.shape, dtype=b.dtype, order="F")
+        n_cols = 1 if b.ndim == 1 else int(b.shape[1])
+        if self.m == 0:
+            return y
+        L.check(L.lib.viprs_plan_dot(self.handle, _FLOAT_CODE[b.dtype], n_cols, _ptr(b), _ptr(y), float(dq_scale),
+                                     int(bool(include_diagonal))))
+        return y
+
+    def last_dot_ms(self):
+        """HIP-event time (ms) of the kernels of the last product on this plan (`dot`, `DeviceState.dot`)."""
+        ms = ctypes.c_double(0.0)
+        L.check(L.lib.viprs_plan_last_dot_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     # -- one-shot host-buffer E-steps (drop-ins for the Cython entry points) -------------------
     def e_step(self, std_beta, var_gamma, var_mu, eta, q, eta_diff, u_logs, sqrt_half_var_tau, mu_mult,
                dq_scale, threads=1, low_memory=None):
@@ -621,6 +647,17 @@ class DeviceState:
                                              int(bool(sync))))
         else:
             L.check(L.lib.viprs_state_e_step(self._h, float(dq_scale), None, 0, int(bool(sync))))
+
+    def dot(self, name="eta", dq_scale=1.0, include_diagonal=True):
+        """``R @ eta`` with the resident posterior mean as `B` (`viprs_state_dot`): only the ``m x n_cols`` results cross to
+        the host.  ``(m,)`` for spike-and-slab and mixture states, ``(m, G)`` column-major for grid states.  Any field other
+        than ``"eta"`` is refused by the library (ValueError)."""
+        if name not in self.FIELDS:
+            raise ValueError(f"unknown field {name!r}")
+        shape = self._shape("eta")
+        y = np.empty(shape, dtype=self.dtype, order="F" if len(shape) == 2 else "C")
+        L.check(L.lib.viprs_state_dot(self._h, self.FIELDS[name], float(dq_scale), int(bool(include_diagonal)), _ptr(y)))
+        return y
 
     def synchronize(self):
         L.check(L.lib.viprs_state_synchronize(self._h))
