@@ -437,6 +437,41 @@ int viprs_plan_dot(viprs_plan* plan, int float_dtype, int n_cols, const void* b_
 int viprs_state_dot(viprs_state* state, int field, double dq_scale, int include_diagonal, void* y_host);
 int viprs_plan_last_dot_ms(viprs_plan* plan, double* ms);
 
+/* ---- ridge solve: the LDPred-inf estimate, one MINRES per LD block -----------------------------------------------------
+ * Solves (R + diag(shift)) x = b, independently for every LD block of the plan (blocks as viprs_plan_get_blocks lists
+ * them, SNP order), by MINRES (Paige & Saunders 1975), x0 = 0 or the caller's. R = unit diagonal + dq_scale * stored
+ * off-diagonal entries: exactly the matrix of viprs_plan_dot(..., include_diagonal = 1).  What the reference's
+ * LDPredInf.fit() (viprs/model/LDPredInf.py:43-114) asks of scipy's minres over ONE assembled block-diagonal matrix; the
+ * system decouples block by block, so every block has its own scalars, its own stopping decision and its own iteration
+ * count, and all blocks advance in lock step: one LD product and one fused kernel per iteration on the plan's stream.
+ *   b, x0, x   (m,) in the state precision `float_dtype`; shift (m,) double, rounded to the state precision
+ *              (y_j = (R v)_j + fl(shift_j) v_j); x0 may be NULL
+ *   per block  r1 = y = b - A x0, beta1 = ||y||; every iteration: v = y / beta, y = A v, (itn >= 2) y -= (beta / oldb) r1,
+ *              alfa = v.y, y -= (alfa / beta) r2, r1 <- r2 <- y, oldb <- beta, beta = ||y||, the Givens rotation of
+ *              (oldeps, delta, gbar, epsln, dbar, gamma, cs, sn, phi, phibar), w = (v - oldeps w1 - delta w2) / gamma,
+ *              x += phi w; the block stops when phibar <= rtol ||b|| (||b|| = beta1 unless x0 is given) or beta == 0
+ *   precision  vectors and the product in the state precision; every scalar and every dot product in double
+ *   order      dot products: 16-byte chunks of the block dealt to 256 threads in turn, per-thread partial sums in ascending
+ *              order, an xor butterfly over the 64 lanes, the wavefronts in order -- a function of the block's size alone;
+ *              no floating-point atomics.  A block's result does not depend on the other blocks of the plan, on
+ *              `check_every` or on timing; two calls give identical bits
+ *   outputs    block_iters / block_relres / block_status (each may be NULL), one entry per block: iterations done, the
+ *              solver's own estimate phibar / ||b|| of the relative residual, and 0 converged, 1 stopped at max_iter,
+ *              2 zero right-hand side (x = 0, 0 iterations)
+ *   host loop  the number of blocks still running is read back every `check_every` iterations (the only synchronisation
+ *              inside the loop); a block whose status is final is frozen: later launches leave it unchanged
+ * viprs_plan_set_active_blocks does NOT filter the solve.  The workspace lives on the plan and is reused.  The dense blocks of
+ * the upper form are read in whichever storage the last sweep left them, as by the product.
+ * Bad dtype code, rtol <= 0, max_iter < 1, check_every < 1, a null plan / b / shift / x: VIPRS_EINVAL before any launch,
+ * outputs untouched.  An empty plan returns VIPRS_OK.
+ *   viprs_plan_last_solve_ms  HIP-event time from the first to the last kernel of the last solve on this plan (the
+ *                             read-backs of the loop included) and the iterations it launched */
+int viprs_plan_solve_ridge(viprs_plan* plan, int float_dtype, const void* b_host, const double* shift_host,
+                           const void* x0_host /* nullable */, void* x_host, double dq_scale, double rtol,
+                           int max_iter, int check_every,
+                           int32_t* block_iters, double* block_relres, int32_t* block_status /* each nullable */);
+int viprs_plan_last_solve_ms(viprs_plan* plan, double* total_ms, int* iterations);
+
 /* ---- measurement support: synthetic LD generated on the device (bench.py, tests) --------------
  * The "longrange" LD blocks of viprs_amd/utils/synthetic.py (the workload of BASELINE.json's configs, SURVEY.md 8d: the
  * reference gets its LD from magenpy stores, VIPRS.py:151-172, none of which exists here) written straight into a plan's

@@ -56,8 +56,10 @@ int build_dot_tables(viprs_plan* P) {
     return VIPRS_OK;
 }
 
-// the kernels of one product on the plan's stream, between the product's own two events
-int enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal) {
+}  // namespace
+
+// the kernels of one product on the plan's stream, between the product's own two events (internal.h: the ridge solve calls it too)
+int viprs::enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal) {
     int rc = build_dot_tables(P);
     if (rc != VIPRS_OK) return rc;
     // Upper form: a plan nobody has swept yet holds the zero lower triangle only because the repack left it so -- mirror it
@@ -82,8 +84,6 @@ int enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void
     P->dot_timed = true;
     return VIPRS_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

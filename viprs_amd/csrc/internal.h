@@ -73,6 +73,24 @@ template <typename V> struct DevBuf {
     }
 };
 
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    ~DevEvent() { if (e) (void)hipEventDestroy(e); }
+};
+
+// ridge solve (abi_ridge.hip, ridge.h): the workspace of a plan, allocated by its first solve and reused by the later ones
+struct RidgeWork {
+    bool built = false;
+    DevBuf<char> d_blocks, d_rec;                  // RidgeBlock / RidgeRec per LD block, SNP order
+    DevBuf<int32_t> d_live;                        // blocks still running
+    size_t vec_bytes = 0;                          // capacity of each vector below
+    DevBuf<char> d_vec[9];                         // v, R v, three residual and three direction vectors in rotation, x
+    DevBuf<char> d_shift;
+    DevEvent ev[2];
+    bool timed = false;
+    int iterations = 0;                            // iterations the last solve launched
+};
+
 }  // namespace viprs
 
 struct viprs_state;
@@ -162,6 +180,7 @@ struct viprs_plan {
     hipEvent_t ev_dot[2] = {nullptr, nullptr};
     bool dot_timed = false;
     bool unmirrored_wanted = false;                // the last launch that asked for a storage of the upper form wanted the zero lower triangle
+    viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
 
     ~viprs_plan();
 };
@@ -239,6 +258,10 @@ int team_launch_done(viprs_plan* P);
 
 // after a synchronisation point: did a team hand-off give up (bounded spin)?
 int check_device_error(viprs_plan* P);
+
+// abi_dot.hip: the kernels of one LD product on the plan's stream (device pointers, (m, n_cols) column-major), between the
+// product's own two events; nothing is synchronised
+int enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal);
 
 // comm.hip: all-gather + rank-ordered reduction of the device vector (n doubles, in place) on `stream`; the last
 // element of every `group` is a maximum, the others are sums

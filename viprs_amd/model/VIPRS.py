@@ -25,6 +25,7 @@ import numpy as np
 
 from ..parallel import BlockShard, LocalComm, broadcast_from_root, shard_blocks
 from ..utils.optim import ConditionStreak, OptimizeResult
+from ._ld_loading import dequantize_scale, ld_load_dtype, load_ld_arrays
 
 logger = logging.getLogger(__name__)
 
@@ -133,11 +134,7 @@ class VIPRS:
         loaded = {}
         for c in all_chroms:
             ld_mat = ld_mats[c]
-            if dequantize_on_the_fly and np.issubdtype(ld_mat.stored_dtype, np.integer):
-                dtype = ld_mat.stored_dtype
-            else:
-                dtype = float_precision
-                dequantize_on_the_fly = False
+            dtype, dequantize_on_the_fly = ld_load_dtype(ld_mat, dequantize_on_the_fly, float_precision)
             expand = bool(expand_ld_on_device) and not low_memory
             # a store that can hand out row ranges (viprs_amd.io.zarr_ld.ZarrLDMatrix): with several ranks only the
             # index is read here, the LD entries of this rank's blocks after the blocks have been dealt out
@@ -148,16 +145,8 @@ class VIPRS:
                 loaded[c] = (None, np.asarray(ld_mat.indptr()), np.arange(1, self._all_shapes[c] + 1, dtype=np.int32),
                              ld_mat, dtype)
             else:
-                if not expand:
-                    try:
-                        lop = ld_mat.load(return_symmetric=not low_memory, dtype=dtype)
-                    except ValueError:
-                        if low_memory or expand_ld_on_device is False:
-                            raise
-                        expand = True
-                if expand:
-                    lop = ld_mat.load(return_symmetric=False, dtype=dtype)
-                    self._expanded = True
+                lop, expanded = load_ld_arrays(ld_mat, low_memory, dtype, expand, expand_ld_on_device)
+                self._expanded = self._expanded or expanded
                 loaded[c] = (lop.ld_data, lop.ld_indptr, lop.leftmost_idx, None, dtype)
             if lambda_min is None:
                 self.lambda_min = 0.0
@@ -208,10 +197,7 @@ class VIPRS:
                 self.std_beta[c] = sh.take(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T)
             del data
         self.dequantize_on_the_fly = dequantize_on_the_fly
-        if dequantize_on_the_fly:
-            self.dequantize_scale = 1.0 / np.iinfo(ld_mats[all_chroms[0]].stored_dtype).max              # :203-207
-        else:
-            self.dequantize_scale = 1.0
+        self.dequantize_scale = dequantize_scale(ld_mats[all_chroms[0]], dequantize_on_the_fly)          # :203-207
 
         self._plans, self._dstate = {}, {}
         if e_step_fn is None:

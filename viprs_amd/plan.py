@@ -54,6 +54,27 @@ def plan_blocks(ld_left_bound, ld_indptr, low_memory):
     return starts[: n.value + 1].copy(), kinds[: n.value].copy()
 
 
+class RidgeInfo:
+    """What a ridge solve reports: per LD block (SNP order) `iterations`, `relres` (the solver's own estimate of
+    ||b - A x|| / ||b||) and `status` (0 converged, 1 stopped at maxiter, 2 zero right-hand side); `converged`: no block
+    stopped at maxiter; `ms`: device time of the solve."""
+    CONVERGED, MAXITER, ZERO_RHS = 0, 1, 2
+
+    def __init__(self, iterations, relres, status, ms=0.0):
+        self.iterations = np.asarray(iterations, dtype=np.int32)
+        self.relres = np.asarray(relres, dtype=np.float64)
+        self.status = np.asarray(status, dtype=np.int32)
+        self.ms = float(ms)
+
+    @property
+    def converged(self):
+        return bool(np.all(self.status != self.MAXITER))
+
+    def __repr__(self):
+        return (f"RidgeInfo(blocks={self.status.shape[0]}, converged={self.converged}, "
+                f"max_iterations={int(self.iterations.max(initial=0))}, ms={self.ms:.3f})")
+
+
 class LDPlan:
     """Device-resident LD matrix of one chromosome (or any set of LD blocks)."""
 
@@ -254,6 +275,53 @@ class LDPlan:
         ms = ctypes.c_double(0.0)
         L.check(L.lib.viprs_plan_last_dot_ms(self.handle, ctypes.byref(ms)))
         return ms.value
+
+    # -- ridge solve -----------------------------------------------------------------------------
+    def solve_ridge(self, b, shift, dq_scale=1.0, rtol=None, maxiter=None, x0=None, check_every=4):
+        """``(R + diag(shift)) x = b`` by one MINRES per LD block, all blocks in lock step (`viprs_plan_solve_ridge`; what
+        the reference's ``LDPredInf.fit`` asks of scipy over one assembled matrix).  `b`: ``(m,)`` float32 or float64, `x`
+        has its dtype; `shift`: a scalar or ``(m,)``; `R` as in `dot` with the diagonal.  Defaults: ``rtol`` 1e-5
+        (float32) / 1e-10 (float64), ``maxiter`` 5 x the largest block (scipy's ``5 n``, per block).  Returns
+        ``(x, info)``: `info.iterations / relres / status` per block in SNP order (`RidgeInfo`), `info.converged`, `info.ms`.
+        `set_active_blocks` does not filter the solve."""
+        b = np.asarray(b)
+        if b.dtype not in _FLOAT_CODE:
+            raise ValueError(f"Buffer dtype mismatch for b: expected float32 or float64, got {b.dtype}")
+        if b.shape != (self.m,):
+            raise ValueError(f"b: expected shape ({self.m},), got {b.shape}")
+        b = np.ascontiguousarray(b)
+        sh = np.asarray(shift, dtype=np.float64)
+        if sh.ndim == 0:
+            sh = np.full(self.m, float(sh))
+        if sh.shape != (self.m,):
+            raise ValueError(f"shift: expected a scalar or shape ({self.m},), got {sh.shape}")
+        sh = np.ascontiguousarray(sh)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0)
+            if x0.dtype != b.dtype or x0.shape != b.shape:
+                raise ValueError(f"x0: expected {b.dtype} of shape {b.shape}, got {x0.dtype} of shape {x0.shape}")
+        if rtol is None:
+            rtol = 1e-5 if b.dtype == np.float32 else 1e-10
+        starts = self.blocks()[0]
+        n_blocks = len(starts) - 1
+        if maxiter is None:
+            maxiter = 5 * int(np.max(np.diff(starts))) if n_blocks else 1
+        x = np.empty_like(b)
+        iters = np.zeros(n_blocks, dtype=np.int32)
+        relres = np.zeros(n_blocks, dtype=np.float64)
+        status = np.zeros(n_blocks, dtype=np.int32)
+        L.check(L.lib.viprs_plan_solve_ridge(self.handle, _FLOAT_CODE[b.dtype], _ptr(b), _ptr(sh), _ptr(x0), _ptr(x),
+                                             float(dq_scale), float(rtol), int(maxiter), int(check_every),
+                                             _ptr(iters), _ptr(relres), _ptr(status)))
+        ms = self.last_solve_ms()[0] if self.m else 0.0
+        return x, RidgeInfo(iters, relres, status, ms)
+
+    def last_solve_ms(self):
+        """``(ms, iterations)`` of the last `solve_ridge` on this plan: HIP-event time from its first to its last kernel and
+        the iterations it launched (the largest per-block count, rounded up to the next read-back of the loop)."""
+        ms, n = ctypes.c_double(0.0), ctypes.c_int(0)
+        L.check(L.lib.viprs_plan_last_solve_ms(self.handle, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
 
     # -- one-shot host-buffer E-steps (drop-ins for the Cython entry points) -------------------
     def e_step(self, std_beta, var_gamma, var_mu, eta, q, eta_diff, u_logs, sqrt_half_var_tau, mu_mult,
