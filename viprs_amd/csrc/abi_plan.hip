@@ -219,7 +219,7 @@ static int plan_create_impl(viprs_plan** out, int64_t m, const int32_t* lb, cons
         // rounds 3-5 derived it from the packed upper form's LDS carve; a team of up to 16 members fits any block below it.)
         constexpr int kMaxDenseBlock = 13184;
         static_assert(kMaxDenseBlock % kPanel == 0, "whole panels");
-        static_assert(kMaxDenseBlock + kStrip + panel_lds_floats(kStrip, true) + kMixLdsFloats <= 160 * 1024 / 4, "the symmetric form fits one workgroup");
+        static_assert(PanelLds(kMaxDenseBlock + 2 * kStrip, true, false).total_floats() <= 160 * 1024 / 4, "the symmetric form fits one workgroup");
         const bool dense = panel_ld && (b.kind == VIPRS_BLOCK_DENSE_SYM || b.kind == VIPRS_BLOCK_DENSE_UPPER) &&
                            d.size <= kMaxDenseBlock;
         if (dense) {

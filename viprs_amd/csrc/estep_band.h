@@ -15,7 +15,8 @@
 // are applied in phase pp + 1 (other panels), by the T-tile at the start of phase pp + 1 (panel pp + 1)
 // or inside the chain (panel pp itself), and phases are separated by workgroup barriers.
 #pragma once
-#include "estep_panel.h"
+#include "panel_loads.h"
+#include "panel_models.h"
 
 namespace viprs {
 

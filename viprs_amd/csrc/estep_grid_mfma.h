@@ -31,7 +31,6 @@
 // streaming form with a lower-pass kernel and an epilogue kernel over the packed upper triangle; removed in round 6.)
 #pragma once
 #include "device_math.h"
-#include "estep_panel.h"
 #include "kernels_common.h"
 
 namespace viprs {

@@ -8,13 +8,16 @@
 //   wave 0 ("chain")     for panel p: q_p  <- LDS; apply a_{p-1} through the 64x64 tile
 //                        R[p-1, p] (64 ordered fma per lane); then the 64 serial SNP updates
 //                        against the diagonal tile R[p, p] -- every lane computes the scalar
-//                        chain redundantly, lane i owns q[p*64 + i], the diagonal-tile rows are
-//                        streamed from HBM 16 rows ahead of their use.
+//                        chain redundantly, lane i owns q[p*64 + i].  Both tiles are in LDS, for
+//                        every model and both forms: the chain wave issues no vector-memory
+//                        instruction for LD inside a panel.
 //   waves 1.. ("updaters") while the chain solves panel p they apply a_{p-1} -- the trailing
 //                        rank-64 update -- to every column RIGHT of panel p: each lane owns 4
 //                        columns, walks the 64 rows of panel p-1 in order (one coalesced 16-byte
 //                        load per lane per row) and performs q[c] = fma(R[j][c], a_j, q[c]);
-//                        they also stage tile R[p, p+1] into LDS for the chain's next phase.
+//                        they also stage the tiles of the chain's next phase into LDS: the diagonal
+//                        tile R[p+1, p+1] (two buffers) and the off-diagonal tile R[p, p+1] (one
+//                        buffer, gated by the chain).
 //
 // Symmetric form: columns LEFT of the current panel (q of SNPs already visited) keep receiving the
 // later rows as well (they are what the next sweep starts from).  Upper-triangular form: the
@@ -26,11 +29,15 @@
 //
 // Large blocks (a single CU pulls only ~50 GB/s from HBM) are shared by a TEAM of TS workgroups on
 // TS CUs: see the comment at `team` in the kernel.
+//
+// Row loads and strip updates: panel_loads.h; the model policies: panel_models.h (both shared with other kernels).
 #pragma once
 #include <type_traits>
 
 #include "device_math.h"
 #include "kernels_common.h"
+#include "panel_loads.h"
+#include "panel_models.h"
 
 #ifndef PANEL_MIN_WAVES
 #define PANEL_MIN_WAVES 2      // waves per SIMD the panel kernel is compiled for (register budget 512 / n): two workgroups per CU
@@ -50,136 +57,6 @@ __device__ unsigned int g_sweep_trace_n;
 #define PPROF(slot, cond) do { } while (0)
 #endif
 
-// ---- 4-element row loads, converted with static_cast<float> as e_step.hpp:173 does ----------
-template <typename U> __device__ __forceinline__ float4 load4(const U* p);
-template <> __device__ __forceinline__ float4 load4<float>(const float* p) {
-    return *reinterpret_cast<const float4*>(p);
-}
-template <> __device__ __forceinline__ float4 load4<int8_t>(const int8_t* p) {
-    const int w = *reinterpret_cast<const int*>(p);
-    return make_float4((float)(int8_t)(w), (float)(int8_t)(w >> 8), (float)(int8_t)(w >> 16),
-                       (float)(int8_t)(w >> 24));
-}
-template <> __device__ __forceinline__ float4 load4<int16_t>(const int16_t* p) {
-    const int2 w = *reinterpret_cast<const int2*>(p);
-    return make_float4((float)(int16_t)(w.x), (float)(int16_t)(w.x >> 16), (float)(int16_t)(w.y),
-                       (float)(int16_t)(w.y >> 16));
-}
-
-// CPL consecutive columns of one row as floats (CPL = 4: one 16-byte load for f32)
-template <int CPL> struct RowVec { float v[CPL]; };
-
-template <typename U, int CPL> __device__ __forceinline__ RowVec<CPL> load_cols(const U* p);
-template <> __device__ __forceinline__ RowVec<4> load_cols<float, 4>(const float* p) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    return RowVec<4>{{t.x, t.y, t.z, t.w}};
-}
-template <> __device__ __forceinline__ RowVec<8> load_cols<float, 8>(const float* p) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    const float4 u = *reinterpret_cast<const float4*>(p + 4);
-    return RowVec<8>{{t.x, t.y, t.z, t.w, u.x, u.y, u.z, u.w}};
-}
-template <> __device__ __forceinline__ RowVec<8> load_cols<int8_t, 8>(const int8_t* p) {
-    const float4 t = load4<int8_t>(p), u = load4<int8_t>(p + 4);
-    return RowVec<8>{{t.x, t.y, t.z, t.w, u.x, u.y, u.z, u.w}};
-}
-template <> __device__ __forceinline__ RowVec<8> load_cols<int16_t, 8>(const int16_t* p) {
-    const float4 t = load4<int16_t>(p), u = load4<int16_t>(p + 4);
-    return RowVec<8>{{t.x, t.y, t.z, t.w, u.x, u.y, u.z, u.w}};
-}
-template <> __device__ __forceinline__ RowVec<2> load_cols<float, 2>(const float* p) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    return RowVec<2>{{t.x, t.y}};
-}
-template <> __device__ __forceinline__ RowVec<1> load_cols<float, 1>(const float* p) { return RowVec<1>{{*p}}; }
-template <> __device__ __forceinline__ RowVec<4> load_cols<int8_t, 4>(const int8_t* p) {
-    const float4 t = load4<int8_t>(p);
-    return RowVec<4>{{t.x, t.y, t.z, t.w}};
-}
-template <> __device__ __forceinline__ RowVec<2> load_cols<int8_t, 2>(const int8_t* p) {
-    const short w = *reinterpret_cast<const short*>(p);
-    return RowVec<2>{{(float)(int8_t)(w), (float)(int8_t)(w >> 8)}};
-}
-template <> __device__ __forceinline__ RowVec<1> load_cols<int8_t, 1>(const int8_t* p) { return RowVec<1>{{(float)*p}}; }
-template <> __device__ __forceinline__ RowVec<4> load_cols<int16_t, 4>(const int16_t* p) {
-    const float4 t = load4<int16_t>(p);
-    return RowVec<4>{{t.x, t.y, t.z, t.w}};
-}
-template <> __device__ __forceinline__ RowVec<2> load_cols<int16_t, 2>(const int16_t* p) {
-    const int w = *reinterpret_cast<const int*>(p);
-    return RowVec<2>{{(float)(int16_t)(w), (float)(int16_t)(w >> 16)}};
-}
-template <> __device__ __forceinline__ RowVec<1> load_cols<int16_t, 1>(const int16_t* p) { return RowVec<1>{{(float)*p}}; }
-
-// value of lane - N within a row of 16 lanes (v_mov_b32_dpp row_shr:N); lanes without a source get `fill`
-template <int N> __device__ __forceinline__ float dpp_shr(float v, float fill) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x110 + N, 0xf, 0xf, false));
-}
-
-// max(x[lane - N], x[lane]) within a row of 16 lanes, lanes without a source keep x (no NaN canonicalisation:
-// the operands are finite); the two wait states a DPP read of a fresh VALU result needs are in the asm
-// Keeps N wave-uniform values (v_readlane results) in SGPRs at this point of the program: the reads are issued together and
-// the scalar chain that consumes them follows without the two wait states a VALU read of a just-written SGPR costs per term.
-template <int N> __device__ __forceinline__ void pin_sgprs(int (&v)[N]) {
-    static_assert(N == 4 || N == 5 || N == 8 || N == 9, "chain lengths of the K <= 8 mixture step");
-    if constexpr (N == 4) asm volatile("" : "+s"(v[0]), "+s"(v[1]), "+s"(v[2]), "+s"(v[3]));
-    if constexpr (N == 5) asm volatile("" : "+s"(v[0]), "+s"(v[1]), "+s"(v[2]), "+s"(v[3]), "+s"(v[4]));
-    if constexpr (N == 8) asm volatile("" : "+s"(v[0]), "+s"(v[1]), "+s"(v[2]), "+s"(v[3]), "+s"(v[4]), "+s"(v[5]), "+s"(v[6]), "+s"(v[7]));
-    if constexpr (N == 9) asm volatile("" : "+s"(v[0]), "+s"(v[1]), "+s"(v[2]), "+s"(v[3]), "+s"(v[4]), "+s"(v[5]), "+s"(v[6]), "+s"(v[7]),
-                                       "+s"(v[8]));
-}
-template <int N> __device__ __forceinline__ float dpp_max_shr(float x) {
-    float r;
-    if (N == 1) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "0"(x));
-    if (N == 2) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_shr:2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "0"(x));
-    if (N == 4) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "0"(x));
-    if (N == 8) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "0"(x));
-    return r;
-}
-
-// r = mask[lane] ? b : a with the lane mask in an SGPR pair (one v_cndmask, no per-step v_cmp)
-__device__ __forceinline__ float sel_mask(float a, float b, unsigned long long m) {
-    float r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(m));
-    return r;
-}
-
-// staged outputs of a team block: another member -- possibly on another XCD, behind another L2 -- copies them into place
-// when the block is done, so they are written past the caches (agent scope)
-__device__ __forceinline__ void stage_store(float* p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ float rl(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// CPL consecutive columns of one LD row exactly as stored (float / int8 / int16), converted with
-// static_cast<float> (e_step.hpp:173) only when consumed: the prefetch buffer of an updater lane holds
-// raw bytes, so a 16-byte load brings 4 fp32, 8 int16 or 16 int8 columns.
-template <typename U, int CPL> struct RawRow {
-    static constexpr int kWords = CPL * (int)sizeof(U) / 4;
-    static_assert(CPL * sizeof(U) % 4 == 0 && (kWords == 1 || kWords == 2 || kWords == 4), "1, 2 or 4 dwords per lane and row");
-    unsigned w[kWords];
-    __device__ __forceinline__ float get(int i) const {
-        if constexpr (sizeof(U) == 4) return __uint_as_float(w[i]);
-        else if constexpr (sizeof(U) == 1) return static_cast<float>(static_cast<int8_t>(w[i >> 2] >> (8 * (i & 3))));
-        else return static_cast<float>(static_cast<int16_t>(w[i >> 1] >> (16 * (i & 1))));
-    }
-};
-template <typename U, int CPL> __device__ __forceinline__ RawRow<U, CPL> load_raw(const U* p) {
-    RawRow<U, CPL> r;
-    if constexpr (RawRow<U, CPL>::kWords == 1) {
-        r.w[0] = *reinterpret_cast<const unsigned*>(p);
-    } else if constexpr (RawRow<U, CPL>::kWords == 2) {
-        const uint2 t = *reinterpret_cast<const uint2*>(p);
-        r.w[0] = t.x; r.w[1] = t.y;
-    } else {
-        const uint4 t = *reinterpret_cast<const uint4*>(p);
-        r.w[0] = t.x; r.w[1] = t.y; r.w[2] = t.z; r.w[3] = t.w;
-    }
-    return r;
-}
 // columns per updater lane: 16-byte loads for fp32 and int16, 8-byte loads for int8 (wider strips leave
 // too few updater waves per block busy)
 template <typename U> __host__ __device__ constexpr int panel_cols() { return sizeof(U) == 4 ? 4 : 8; }
@@ -200,304 +77,6 @@ template <typename U> __host__ __device__ constexpr int panel_team_cols() {
 #endif
 }
 
-constexpr int kChainPrefetch = 16;   // diagonal-tile rows in flight ahead of the serial chain
-#ifndef PANEL_STRIP_DEPTH
-#define PANEL_STRIP_DEPTH 16
-#endif
-constexpr int kStripRowsInFlight = PANEL_STRIP_DEPTH;   // row loads in flight per updater lane (x 16 B for every LD type)
-
-
-// Trailing update of one strip (64 * CPL columns) by one wave: q[c..c+CPL-1] = fma(R[row][c..], a_row, .)
-// for the 64 rows of a panel, in row order, with DEPTH row loads in flight per lane (DEPTH * CPL = 64
-// floats of row data per lane whatever the strip width).  The row loop is rolled in groups of DEPTH
-// so that every load is consumed exactly one group later (a fully unrolled loop lets hipcc sink the
-// loads next to their uses, leaving two in flight), and there is no runtime guard around any load
-// (a guard makes hipcc wait vmcnt(0) per row).  FULL = false (partial last panel of a block): rows
-// past its end are clamped to its last row; their a is 0, so fma(R, 0, q) == q leaves q untouched.
-// MIXED (mirrored upper form, a strip with columns on both sides of the chain): the multiplier of row j is per lane,
-// fvec * avec[j] -- avec = eta_diff of the panel, fvec = 1 for a column left of the chain (a term of its second-pass sum),
-// dq right of it (dq * eta_diff[j] IS a_j, the same product the chain formed): one v_mul per row more.
-template <typename U, int CPL, bool FULL, int DEPTH = kStripRowsInFlight, bool MIXED = false>
-__device__ __forceinline__ void strip_update(const U* __restrict__ rowp, int stride, int last_row, float avec,
-                                             float* __restrict__ lq_c, float fvec = 1.0f) {
-    static_assert(kPanel % DEPTH == 0, "panel must be a whole number of prefetch groups");
-    float qv[CPL];
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) qv[i] = lq_c[i];
-    RawRow<U, CPL> buf[DEPTH];
-#pragma unroll
-    for (int k = 0; k < DEPTH; ++k)
-        buf[k] = load_raw<U, CPL>(rowp + (int64_t)(FULL ? k : min(k, last_row)) * stride);
-#pragma unroll 1
-    for (int g = 0; g < kPanel / DEPTH - 1; ++g) {
-#pragma unroll
-        for (int k = 0; k < DEPTH; ++k) {
-            const RawRow<U, CPL> v = buf[k];
-            const int rn = DEPTH * (g + 1) + k;
-            buf[k] = load_raw<U, CPL>(rowp + (int64_t)(FULL ? rn : min(rn, last_row)) * stride);
-            const float a = MIXED ? fvec * rl(avec, DEPTH * g + k) : rl(avec, DEPTH * g + k);
-#pragma unroll
-            for (int i = 0; i < CPL; ++i) qv[i] = __builtin_fmaf(v.get(i), a, qv[i]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < DEPTH; ++k) {
-        const RawRow<U, CPL> v = buf[k];
-        const float a = MIXED ? fvec * rl(avec, kPanel - DEPTH + k) : rl(avec, kPanel - DEPTH + k);
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) qv[i] = __builtin_fmaf(v.get(i), a, qv[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) lq_c[i] = qv[i];
-}
-
-// Mirrored upper form: the terms of the second-pass sums that lie INSIDE a diagonal tile -- s[i] += R[i, j] ed[j] for the
-// SNPs i < j of one panel, read as R[j, i] from row j (lane = column i), rows in ascending order.  The tile is the one the
-// chain has just swept, still in LDS (fp32, staged rows past a partial last panel clamped; their eta_diff is 0).
-__device__ __forceinline__ float diag_lower_update(const float* __restrict__ tile, float edvec, float sv, int lane) {
-#pragma unroll 16
-    for (int jr = 0; jr < kPanel; ++jr) {
-        const float t = __builtin_fmaf(tile[jr * kPanel + lane], rl(edvec, jr), sv);
-        sv = lane < jr ? t : sv;
-    }
-    return sv;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Model policies: what one SNP update computes (the serial chain evaluates `update` with the
-// lane-select table lookup; after the 64 steps every lane replays its own SNP with the per-lane
-// lookup -- same operations, same inputs, same bits -- and `finish` stores the outputs).
-//   load    per-SNP inputs of SNP j (lane-resident for a whole panel)
-//   update  d = new eta - old eta from the current q[j];  returns false on the skip branch
-//   finish  replay + stores; returns the scaled eta_diff (0 for skipped SNPs)
-// ---------------------------------------------------------------------------------------------
-template <bool EXACT>
-struct SpikeSlabModel {                      // e_step, e_step.hpp:387-433
-    static constexpr bool kLaneParallel = false;
-    struct In { float mm, beta, sv, ulog, eta_old; };
-    static __device__ __forceinline__ In load(const EStepArgs<float>& A, int64_t j, bool live) {
-        In in;
-        in.mm = live ? A.mu_mult[j] : 0.0f;
-        in.beta = live ? A.std_beta[j] : 0.0f;
-        in.sv = live ? A.shvt[j] : 0.0f;
-        in.ulog = live ? A.u_logs[j] : 0.0f;
-        in.eta_old = live ? A.eta[j] : 0.0f;
-        return in;
-    }
-    static constexpr bool kHasSkip = true;     // e_step.hpp:410-413
-    // d = new eta - old eta of the lane's SNP from the current q (no skip handling)
-    template <int LOOKUP>
-    static __device__ __forceinline__ float delta(const In& in, float q, const ExpTab& tab, int sel) {
-        float mu, gamma, d;
-        snp_update<EXACT, LOOKUP>(in.mm, in.beta, in.sv, in.ulog, in.eta_old, q, tab, mu, gamma, d, sel);
-        return d;
-    }
-    template <int LOOKUP>
-    static __device__ __forceinline__ bool update(const In& in, float q, const ExpTab& tab, float& d, int sel) {
-        d = delta<LOOKUP>(in, q, tab, sel);
-        return !(fabsf(d) < Eps<float>::value);                       // :410
-    }
-    template <bool TEAM>
-    static __device__ __forceinline__ float finish(const EStepArgs<float>& A, int64_t j, const In& in, float q,
-                                                   const ExpTab& tab, bool live, bool writer, bool& skipped,
-                                                   float* d_out = nullptr) {
-        float mu, gamma, d;
-        snp_update<EXACT, kLookupPerLane>(in.mm, in.beta, in.sv, in.ulog, in.eta_old, q, tab, mu, gamma, d);
-        const bool skip = fabsf(d) < Eps<float>::value;
-        if (live && writer) {
-            if (!skip) {
-                A.var_mu[j] = mu;                                         // :416-418
-                A.var_gamma[j] = gamma;
-                A.eta_diff[j] = d;
-                if (!TEAM) A.eta[j] = in.eta_old + d;                     // :431
-            } else {
-                A.eta_diff[j] = 0.0f;                                     // :412
-            }
-            if (TEAM) stage_store(A.eta_out + j, skip ? in.eta_old : in.eta_old + d);
-        }
-        skipped = live && skip;
-        if (d_out) *d_out = (live && !skip) ? d : 0.0f;
-        return (live && !skip) ? A.dq * d : 0.0f;
-    }
-};
-
-// One column of e_step_grid (e_step.hpp:599-635): models of a grid are independent, so the host runs
-// this policy once per active model with the (m, G) column-major arrays offset to that column.
-// Different arithmetic from e_step: no fma in mu / the logit / d, half_var_tau instead of its
-// square root, no skip branch.  EXACT = false (math_mode = fast): the sigmoid on v_exp_f32 / v_rcp_f32.
-template <bool EXACT = true>
-struct GridColumnModel {
-    static constexpr bool kLaneParallel = false;
-    struct In { float mm, beta, hvt, ulog, eta_old; };
-    static __device__ __forceinline__ In load(const EStepArgs<float>& A, int64_t j, bool live) {
-        In in;
-        in.mm = live ? A.mu_mult[j] : 0.0f;
-        in.beta = live ? A.std_beta[j] : 0.0f;
-        in.hvt = live ? A.shvt[j] : 0.0f;
-        in.ulog = live ? A.u_logs[j] : 0.0f;
-        in.eta_old = live ? A.eta[j] : 0.0f;
-        return in;
-    }
-    template <int LOOKUP>
-    static __device__ __forceinline__ void core(const In& in, float q, const ExpTab& tab, float& mu, float& gamma,
-                                                float& d, int sel) {
-        mu = in.mm * (in.beta - q);                                       // :613
-        const float u = in.ulog + in.hvt * mu * mu;                       // :616
-        gamma = EXACT ? sigmoid_exact<LOOKUP>(u, tab, sel) : sigmoid_fast(u);   // :617
-        d = gamma * mu - in.eta_old;                                      // :620
-    }
-    static constexpr bool kHasSkip = false;
-    template <int LOOKUP>
-    static __device__ __forceinline__ float delta(const In& in, float q, const ExpTab& tab, int sel) {
-        float mu, gamma, d;
-        core<LOOKUP>(in, q, tab, mu, gamma, d, sel);
-        return d;
-    }
-    template <int LOOKUP>
-    static __device__ __forceinline__ bool update(const In& in, float q, const ExpTab& tab, float& d, int sel) {
-        d = delta<LOOKUP>(in, q, tab, sel);
-        return true;
-    }
-    template <bool TEAM>
-    static __device__ __forceinline__ float finish(const EStepArgs<float>& A, int64_t j, const In& in, float q,
-                                                   const ExpTab& tab, bool live, bool writer, bool& skipped,
-                                                   float* d_out = nullptr) {
-        float mu, gamma, d;
-        core<kLookupPerLane>(in, q, tab, mu, gamma, d, 0);
-        if (d_out) *d_out = live ? d : 0.0f;
-        if (live && writer) {
-            A.var_mu[j] = mu;
-            A.var_gamma[j] = gamma;
-            A.eta_diff[j] = d;
-            if (TEAM) stage_store(A.eta_out + j, in.eta_old + d); else A.eta[j] = in.eta_old + d;   // :633
-        }
-        skipped = false;
-        return live ? A.dq * d : 0.0f;
-    }
-};
-
-template <typename MODEL> struct IsGridColumn : std::false_type {};
-template <bool EXACT> struct IsGridColumn<GridColumnModel<EXACT>> : std::true_type {};
-
-// exp(x), x <= 0, of the softmax (e_step.hpp:231-240): glibc's expf bit for bit, or v_exp_f32 (math_mode = fast)
-template <bool EXACT, int LOOKUP>
-__device__ __forceinline__ float softmax_exp(float x, const ExpTab& tab, int sel = 0) {
-    if constexpr (EXACT) return expf_glibc_nonpos<LOOKUP>(x, tab, sel);
-    else return expf_fast_nonpos(x);
-}
-// e / ssum of the softmax (:239): the IEEE fp32 divide, or e * v_rcp_f32(ssum) (math_mode = fast; 1 ulp + 1 rounding)
-template <bool EXACT>
-__device__ __forceinline__ float softmax_div(float e, float ssum) {
-    if constexpr (EXACT) return e / ssum;
-    else return e * __builtin_amdgcn_rcpf(ssum);
-}
-
-// e_step_mixture (e_step.hpp:496-537) for K <= kPanelMaxK components ((m, K) arrays C-ordered).
-template <bool EXACT = true>
-struct MixtureModel {
-    static constexpr bool kExact = EXACT;
-    // the chain evaluates the K + 1 components of ONE SNP on K + 1 lanes (see the chain in panel_role)
-    static constexpr bool kLaneParallel = true;
-    struct In { float mm[kPanelMaxK], sv[kPanelMaxK], ulog[kPanelMaxK]; float lnp, beta, eta_old; int K; };
-    static __device__ __forceinline__ In load(const EStepArgs<float>& A, int64_t j, bool live) {
-        In in;
-        in.K = A.width;
-#pragma unroll
-        for (int k = 0; k < kPanelMaxK; ++k) {
-            const bool on = live && k < in.K;
-            const int64_t idx = on ? j * in.K + k : 0;
-            in.mm[k] = on ? A.mu_mult[idx] : 0.0f;
-            in.sv[k] = on ? A.shvt[idx] : 0.0f;
-            in.ulog[k] = on ? A.u_logs[idx] : 0.0f;
-        }
-        in.lnp = live ? A.log_null_pi[j] : 0.0f;
-        in.beta = live ? A.std_beta[j] : 0.0f;
-        in.eta_old = live ? A.eta[j] : 0.0f;
-        return in;
-    }
-    template <int LOOKUP>
-    static __device__ __forceinline__ void core(const In& in, float q, const ExpTab& tab, float (&mu)[kPanelMaxK],
-                                                float (&gam)[kPanelMaxK], float& d, int sel) {
-        const float r = in.beta - q;                                      // :505
-        float u[kPanelMaxK];
-        float mx = in.lnp;                                                // max over u_0..u_K (c_max, :58-71)
-#pragma unroll
-        for (int k = 0; k < kPanelMaxK; ++k) {
-            mu[k] = in.mm[k] * r;                                         // :509
-            const float t = in.sv[k] * mu[k];
-            u[k] = __builtin_fmaf(t, t, in.ulog[k]);                      // :511
-            if (k < in.K) mx = fmaxf(mx, u[k]);
-        }
-        float ssum = 0.0f;                                                // softmax, :231-240: k = 0..K in order
-#pragma unroll
-        for (int k = 0; k < kPanelMaxK; ++k) {
-            if (k < in.K) {
-                u[k] = softmax_exp<EXACT, LOOKUP>(u[k] - mx, tab, sel);
-                ssum += u[k];
-            }
-        }
-        ssum += softmax_exp<EXACT, LOOKUP>(in.lnp - mx, tab, sel);
-        d = -in.eta_old;                                                  // :519
-#pragma unroll
-        for (int k = 0; k < kPanelMaxK; ++k) {
-            if (k < in.K) {
-                gam[k] = softmax_div<EXACT>(u[k], ssum);                  // :239
-                d = __builtin_fmaf(gam[k], mu[k], d);                     // :523
-            }
-        }
-    }
-    template <int LOOKUP>
-    static __device__ __forceinline__ bool update(const In& in, float q, const ExpTab& tab, float& d, int sel) {
-        float mu[kPanelMaxK], gam[kPanelMaxK];
-        core<LOOKUP>(in, q, tab, mu, gam, d, sel);
-        return true;
-    }
-    template <bool TEAM>
-    static __device__ __forceinline__ float finish(const EStepArgs<float>& A, int64_t j, const In& in, float q,
-                                                   const ExpTab& tab, bool live, bool writer, bool& skipped) {
-        float mu[kPanelMaxK], gam[kPanelMaxK], d;
-        core<kLookupPerLane>(in, q, tab, mu, gam, d, 0);
-        if (live && writer) {
-#pragma unroll
-            for (int k = 0; k < kPanelMaxK; ++k) {
-                if (k < in.K) {
-                    A.var_mu[j * in.K + k] = mu[k];
-                    A.var_gamma[j * in.K + k] = gam[k];
-                }
-            }
-            A.eta_diff[j] = d;
-            if (TEAM) stage_store(A.eta_out + j, in.eta_old + d); else A.eta[j] = in.eta_old + d;   // :536
-        }
-        skipped = false;
-        return live ? A.dq * d : 0.0f;
-    }
-};
-
-// e_step_mixture for kPanelMaxK < K <= kPanelWideMaxK components: the K + 1 components of one SNP on K + 1 lanes as
-// in MixtureModel, but (i) the component inputs of the coming SNPs are prefetched from global memory into a ring of
-// registers (the (m, K) arrays keep a SNP's K values contiguous: one 128-byte line per SNP and array) and the
-// per-component outputs are stored straight from the chain -- no LDS staging that would grow with K; (ii) the
-// reference's ordered sums (softmax denominator e_step.hpp:231-240, eta :519-523) run as scalar chains over
-// v_readlane values: KMAX terms whatever K is -- the terms of lanes > K are exactly neutral (e = +0, gamma = 0).
-template <int KMAX>
-struct MixtureWideModel {
-    static constexpr bool kLaneParallel = true;
-    static constexpr bool kWide = true;
-    static constexpr int kMax = KMAX;
-    struct In { float lnp, beta, eta_old; int K; };
-    static __device__ __forceinline__ In load(const EStepArgs<float>& A, int64_t j, bool live) {
-        In in;
-        in.K = A.width;
-        in.lnp = live ? A.log_null_pi[j] : 0.0f;
-        in.beta = live ? A.std_beta[j] : 0.0f;
-        in.eta_old = live ? A.eta[j] : 0.0f;
-        return in;
-    }
-};
-template <typename M, typename = void> struct is_wide_mixture { static constexpr bool value = false; };
-template <typename M> struct is_wide_mixture<M, std::enable_if_t<M::kWide>> { static constexpr bool value = true; };
-
 // One role of the sweep kernel below: a workgroup either works as member `wg % team_size` of team `wg / team_size`
 // on the statically assigned blocks of a team class (TEAM), or pulls blocks from the small-block queue.
 // FORM: what the LD buffer holds and which arithmetic runs over it --
@@ -513,34 +92,26 @@ constexpr int kFormSym = 1, kFormMirror = 2;
 
 template <typename U, typename MODEL, int FORM, int NW, bool TEAM, int CPL>
 __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int qcap, float* __restrict__ smem, const int wg) {
-    // q[qcap] | a[2][64] | tiles[2][64 x 64] | mixture chain scratch.  The two tile buffers hold
-    //   lane-per-SNP models: the DIAGONAL tiles R[p, p] / R[p+1, p+1] (staged by the updaters one phase ahead; the
-    //     chain reads its row with one ds_read per step and touches no LD memory on its critical path -- the
-    //     off-diagonal tile R[p, p+1] of its next phase it prefetches into registers, one row per step, a whole
-    //     phase ahead of its use);
-    //   mixtures (rolled chain loop): the same since round 4 (before: the off-diagonal tiles R[p-1, p] / R[p, p+1] here and the
-    //     diagonal rows streamed from global memory by the chain wave; -DPANEL_MIX_UPPER_REGS keeps that for the upper form).
-    // (the buffer holds both triangles in either form: strips left and right of the chain)
+    // q[qcap] | a[2][64] | diagonal tiles[2][64 x 64] | off-diagonal tile[64 x 64] | mixture chain scratch.  For every
+    // model (lane per SNP, the K <= 8 mixture with the components of one SNP across the lanes, the wide mixtures K = 9 .. 31)
+    // and both forms:
+    //   the two diagonal-tile buffers hold R[p, p] / R[p+1, p+1], staged by the updaters one phase ahead; the chain reads
+    //     its row with one ds_read per step;
+    //   the single off-diagonal buffer holds R[p, p+1], the tile the chain's NEXT phase starts with, staged by the
+    //     updaters during phase p once the chain has consumed its predecessor (s_tdone below).
+    // The chain wave issues no vector-memory instruction for LD inside a panel.
+    // (the LD buffer holds both triangles in either form: strips left and right of the chain)
     constexpr bool MIR = FORM == kFormMirror;       // the arithmetic is the upper-triangular form's
     constexpr bool SUMS = FORM != kFormSym;         // second-pass sums s[] and eta_diff of the last two panels in LDS
-    constexpr bool kDiagInLds = !MODEL::kLaneParallel;
-    // The off-diagonal tile of the chain's next phase goes through LDS too (below), for every model and both forms: the
-    // chain wave issues no vector-memory instruction inside a panel.  The K <= 8 mixture chain (components of one SNP across
-    // the lanes) and the wide mixtures (K = 9 .. 31) follow the same scheme: diagonal tiles staged in LDS, the off-diagonal
-    // tile of the next phase in the single gated buffer.
-    constexpr bool kMixLds = MODEL::kLaneParallel;
-    constexpr bool kStageDiag = kDiagInLds || kMixLds;          // what the updaters stage into lT: diagonal tiles
-    float* lq = smem;
-    float* la = smem + qcap;
-    float* lT = la + 2 * kPanel;
-    // lane-per-SNP models: the off-diagonal tile R[p, p+1] the chain's NEXT phase starts with (ONE buffer: staged by the
-    // updaters during phase p once the chain has consumed its predecessor -- s_tdone below)
-    float* lTo = lT + 2 * kPanel * kPanel;
-    float* lmx = lTo + kPanel * kPanel;                      // mixture chain only (kMixLdsFloats)
+    const PanelLds lds(qcap, MODEL::kLaneParallel && !is_wide_mixture<MODEL>::value, MIR);
+    float* lq = smem + lds.q();
+    float* la = smem + lds.a();
+    float* lT = smem + lds.diag_tiles();
+    float* lTo = smem + lds.offdiag_tile();
+    float* lmx = smem + lds.mix();                           // K <= 8 mixture chain only
     // upper-triangular form: eta_diff of the last two panels and the running second-pass sums s[j] of the block
-    // (panel_mirror_lds_floats; behind the mixture scratch)
-    float* led = lmx + ((MODEL::kLaneParallel && !is_wide_mixture<MODEL>::value) ? kMixLdsFloats : 0);
-    float* ls = led + 2 * kPanel;
+    float* led = smem + lds.ed();
+    float* ls = smem + lds.s();
     // row loads in flight per updater lane: 64 VGPRs of row data whatever the strip width (team strips are narrower, see
     // panel_team_cols: more rows in flight, fewer memory round trips per phase on the critical path)
 #ifdef PANEL_TEAM_STRIP_DEPTH
@@ -638,30 +209,22 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
             if (SUMS) ls[li] = 0.0f;
         }
         if (tid == 0) { s_tdone = 0; s_ddone = 0; }
-        if (kStageDiag) {
-            // diagonal tile of panel 0 (rows past the end of a short block are clamped: finite values that
-            // only ever meet a = 0)
-            for (int i = tid; i < kPanel * kPanel / 4; i += NW * 64) {
-                const int row = i >> 4, tcol = (i & 15) * 4;
-                *reinterpret_cast<float4*>(lT + row * kPanel + tcol) = load4<U>(base + (int64_t)min(row, b - 1) * stride + tcol);
-            }
+        // diagonal tile of panel 0 (rows past the end of a short block are clamped: finite values that
+        // only ever meet a = 0)
+        for (int i = tid; i < kPanel * kPanel / 4; i += NW * 64) {
+            const int row = i >> 4, tcol = (i & 15) * 4;
+            *reinterpret_cast<float4*>(lT + row * kPanel + tcol) = load4<U>(base + (int64_t)min(row, b - 1) * stride + tcol);
         }
         __syncthreads();
 
         float a_prev = 0.0f;   // chain wave: lane j = dq * eta_diff of SNP j of the previous panel
 
-        // ---- chain wave: inputs and first diagonal-tile rows of the NEXT panel, fetched under the
-        //      current panel's serial updates so that no HBM latency sits between two panels
+        // ---- chain wave: per-SNP inputs of the NEXT panel, fetched under the current panel's serial
+        //      updates so that no HBM latency sits between two panels
         typename MODEL::In nxt_in{};
-        float dnext[kChainPrefetch];                    // mixture chain: first diagonal rows of the next panel
         if (wave == 0) {
             const bool live0 = lane < b;
             nxt_in = MODEL::load(A, s0 + (live0 ? lane : 0), live0);
-            if (!kStageDiag) {
-#pragma unroll
-                for (int k = 0; k < kChainPrefetch; ++k)
-                    dnext[k] = static_cast<float>(base[(int64_t)min(k, b - 1) * stride + lane]);
-            }
         }
 
         // symmetric form: one extra phase applies the last panel's a-vector to the columns left of it
@@ -691,22 +254,9 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                         nxt_in = MODEL::load(A, s0 + (ln ? rn : 0), ln);
                     }
 
-                    // diagonal tile rows, streamed kChainPrefetch rows ahead.  All 64 steps always
-                    // run, straight-line (no runtime guards around loads, see strip_update): rows
-                    // past a partial last panel are clamped and their steps forced onto the skip
-                    // path (a = 0 leaves every q untouched).
-                    const int last = nrows - 1;
-                    const U* __restrict__ dptr = base + (int64_t)r0 * stride + r0 + lane;
-                    float drow[kStageDiag ? 1 : kPanel];
-                    if (!kStageDiag) {
-#pragma unroll
-                        for (int k = 0; k < kChainPrefetch; ++k) drow[k] = dnext[k];
-                    }
-                    // first rows of the next panel's diagonal tile (clamped to the block when there
-                    // is no next panel: loaded, never used)
-                    const int rn0 = min(r0 + kPanel, bpad - kPanel);
-                    const U* __restrict__ nptr = base + (int64_t)rn0 * stride + rn0 + lane;
-
+                    // All 64 steps of a panel always run, straight-line: the staged rows past a partial
+                    // last panel are clamped and their steps forced onto the skip path (a = 0 leaves
+                    // every q untouched).
                     float qc;
                     // mirrored upper form: lane j keeps the q_j its own update consumed (what the upper form leaves in q[j] until
                     // the second pass is added)
@@ -787,12 +337,11 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                             return arr + min(s0 + r0 + jj, jlast) * K + kc;
                         };
                         static_assert(kChainPrefetch == 16 && kPanel == 64, "window indexing");
-                        float win[kChainPrefetch], rmm[kChainPrefetch], rsv[kChainPrefetch], rul[kChainPrefetch];
+                        float rmm[kChainPrefetch], rsv[kChainPrefetch], rul[kChainPrefetch];
                         float rvec = in.beta - qc;                         // lane j: beta_j - q_j, read by step j (:505)
-                        const float* __restrict__ DtW = lT + (p & 1) * kPanel * kPanel + lane;    // kMixLds: the panel's diagonal tile in LDS
+                        const float* __restrict__ DtW = lT + (p & 1) * kPanel * kPanel + lane;    // the panel's diagonal tile in LDS
 #pragma unroll
                         for (int k = 0; k < kChainPrefetch; ++k) {
-                            win[k] = kMixLds ? 0.0f : drow[kMixLds ? 0 : k];
                             rmm[k] = *cptr(A.mu_mult, k);
                             rsv[k] = *cptr(A.shvt, k);
                             rul[k] = *cptr(A.u_logs, k);
@@ -802,15 +351,9 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
 #pragma unroll
                         for (int k = 0; k < kChainPrefetch; ++k) {
                             const int jj = kChainPrefetch * g + k;                             // wave-uniform
-                            const float drow_jj = kMixLds ? DtW[jj * kPanel] : win[k];
+                            const float drow_jj = DtW[jj * kPanel];
                             const float cmm = rmm[k], csv = rsv[k], cul = rul[k];
                             {
-                                if (!kMixLds) {
-                                    const U* __restrict__ src = (g < kPanel / kChainPrefetch - 1)
-                                        ? dptr + (int64_t)min(jj + kChainPrefetch, last) * stride
-                                        : nptr + (int64_t)min(k, b - 1 - rn0) * stride;
-                                    win[k] = static_cast<float>(*src);
-                                }
                                 // (the ring runs on into the next panel; past the block it re-reads the last SNP)
                                 rmm[k] = *cptr(A.mu_mult, jj + kChainPrefetch);
                                 rsv[k] = *cptr(A.shvt, jj + kChainPrefetch);
@@ -881,10 +424,6 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                             if (!MIR) qc = (me && livej) ? qc - d : qc;                 // :527
                         }
                         }
-                        if (!kMixLds) {
-#pragma unroll
-                            for (int k = 0; k < kChainPrefetch; ++k) dnext[k] = win[k];
-                        }
                         if (member == 0 && live) {
                             A.eta_diff[j] = dvec;
                             if (TEAM) stage_store(A.eta_out + j, in.eta_old + dvec); else A.eta[j] = in.eta_old + dvec;   // :536
@@ -924,31 +463,15 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                         constexpr bool K4 = decltype(k4_c)::value;
                         float rvec = in.beta - qc;                         // lane j: beta_j - q_j, read by step j (:505)
                         // Rolled in 4 groups of kChainPrefetch = 16 steps (the fully unrolled mixture chain does
-                        // not fit the instruction cache): the row consumed at step 16 g + k was loaded 16 steps
-                        // earlier into the same register win[k]; the last group loads the first rows of the NEXT
-                        // panel's diagonal tile, which are handed over through dnext.
-                        static_assert(kChainPrefetch == 16 && kPanel == 64, "window indexing");
-                        float win[kMixLds ? 1 : kChainPrefetch];
-                        if (!kMixLds) {
-#pragma unroll
-                            for (int k = 0; k < kChainPrefetch; ++k) win[k] = drow[kMixLds ? 0 : k];
-                        }
-                        const float* __restrict__ Dt = lT + (p & 1) * kPanel * kPanel + lane;     // kMixLds: diagonal tile of the panel
+                        // not fit the instruction cache).
+                        static_assert(kChainPrefetch == 16 && kPanel == 64, "group indexing");
+                        const float* __restrict__ Dt = lT + (p & 1) * kPanel * kPanel + lane;     // diagonal tile of the panel
 #pragma unroll 1
                         for (int g = 0; g < kPanel / kChainPrefetch; ++g) {
 #pragma unroll
                         for (int k = 0; k < kChainPrefetch; ++k) {
                             const int jj = kChainPrefetch * g + k;                             // wave-uniform
-                            float drow_jj;
-                            if (kMixLds) {
-                                drow_jj = Dt[jj * kPanel];
-                            } else {
-                                drow_jj = win[kMixLds ? 0 : k];
-                                const U* __restrict__ src = (g < kPanel / kChainPrefetch - 1)
-                                    ? dptr + (int64_t)min(jj + kChainPrefetch, last) * stride
-                                    : nptr + (int64_t)min(k, b - 1 - rn0) * stride;
-                                win[kMixLds ? 0 : k] = static_cast<float>(*src);
-                            }
+                            const float drow_jj = Dt[jj * kPanel];
                             const int jn = (jj + 1 < kPanel) ? jj + 1 : jj;
                             const float nmm = Lmm[jn * K + kc], nsv = Lsv[jn * K + kc], nul = Lul[jn * K + kc];
                             const float lnp = rl(in.lnp, jj), eta_old = rl(in.eta_old, jj);
@@ -1021,10 +544,6 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                             if (!MIR) qc = (me && livej) ? qc - d : qc;                 // :527
                             cmm = nmm; csv = nsv; cul = nul;
                         }
-                        }
-                        if (!kMixLds) {
-#pragma unroll
-                            for (int k = 0; k < kChainPrefetch; ++k) dnext[k] = win[kMixLds ? 0 : k];
                         }
                         };
                         if (K == 4) run_panel(std::integral_constant<int, 4>{}, std::true_type{});
@@ -1105,13 +624,13 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                 // ================================ updaters ===================================
                 const int uw = wave - 1;
                 auto stage_tiles = [&]() {
-                // stage the tile of the chain's next phase: the diagonal tile R[p+1, p+1] (lane-per-SNP models) or the
-                // off-diagonal tile R[p, p+1] (mixture).  16 row groups of 4 rows dealt to the updater waves, all of a
-                // wave's loads issued before its first LDS store (one memory round trip per phase)
+                // stage the tiles of the chain's next phase: the diagonal tile R[p+1, p+1] and the off-diagonal tile
+                // R[p, p+1].  16 row groups of 4 rows dealt to the updater waves, all of a wave's loads issued before
+                // its first LDS store (one memory round trip per phase)
                 if (p + 1 < np) {
                     float* __restrict__ T = lT + ((p + 1) & 1) * kPanel * kPanel;
                     const int trow = lane >> 4, tcol = (lane & 15) * 4;
-                    const int row_base = (kStageDiag ? p + 1 : p) * kPanel;
+                    const int row_base = (p + 1) * kPanel;
                     constexpr int kGroups = (kPanel / 4 + NW - 2) / (NW - 1);
                     float4 v[kGroups];
 #pragma unroll

@@ -18,8 +18,8 @@
 #pragma once
 #include "device_math.h"
 #include "estep_generic.h"
-#include "estep_panel.h"        // RawRow / load_raw, the model policies' helpers
 #include "kernels_common.h"
+#include "panel_loads.h"         // RawRow / load_raw
 
 namespace viprs {
 

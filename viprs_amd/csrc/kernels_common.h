@@ -107,17 +107,29 @@ constexpr int kPanel = 64;          // SNPs per panel = lanes per wavefront on g
 constexpr int kStrip = 256;         // padding unit of the per-block q arrays (one fp32 updater strip: 64 lanes x 4 columns)
 
 // ---- sizes the host-side schedule shares with the kernel headers ------------------------------------
-// panel kernels (estep_panel.h): LDS carve (floats) q[qcap] | a[2][64] | T[2][64*64]
-// (+ To[64*64], the off-diagonal tile of the chain's next phase, for the lane-per-SNP models: `offdiag_tile`)
-__host__ __device__ constexpr int panel_lds_floats(int qcap, bool offdiag_tile = false) {
-    return qcap + 2 * kPanel + 2 * kPanel * kPanel + (offdiag_tile ? kPanel * kPanel : 0);
-}
-// upper-triangular form over mirrored storage (kFormMirror): eta_diff of the last two panels and the sums s[qcap]
-__host__ __device__ constexpr int panel_mirror_lds_floats(int qcap) { return 2 * kPanel + qcap; }
 constexpr int kPanelMaxK = 8;       // mixture components the lane-parallel panel chain handles with its inputs staged in LDS
 constexpr int kPanelWideMaxK = 31;  // ... and with scalar chains over v_readlane values (MixtureWideModel)
 // LDS of the lane-parallel mixture chain: mu_mult | sqrt_half_var_tau | u_logs | var_mu | var_gamma, [64 SNPs][K]
 constexpr int kMixLdsFloats = 5 * kPanel * kPanelMaxK;
+// The dynamic LDS of the panel kernels (estep_panel.h) as float offsets: the kernel takes its pointers from it, the
+// launcher its size.
+//   q[qcap] | a[2][64] | diagonal tiles[2][64 x 64] | off-diagonal tile[64 x 64] | mixture scratch | ed[2][64] | s[qcap]
+// mix_scratch: the K <= 8 mixture chain (MixtureModel) stages its component inputs and outputs; mirror: the upper-
+// triangular form over mirrored storage (kFormMirror) keeps eta_diff of the last two panels and the second-pass sums s.
+struct PanelLds {
+    int qcap;
+    bool mix_scratch, mirror;
+    __host__ __device__ constexpr PanelLds(int qcap_, bool mix_scratch_, bool mirror_)
+        : qcap(qcap_), mix_scratch(mix_scratch_), mirror(mirror_) {}
+    __host__ __device__ constexpr int q() const { return 0; }
+    __host__ __device__ constexpr int a() const { return qcap; }
+    __host__ __device__ constexpr int diag_tiles() const { return a() + 2 * kPanel; }
+    __host__ __device__ constexpr int offdiag_tile() const { return diag_tiles() + 2 * kPanel * kPanel; }
+    __host__ __device__ constexpr int mix() const { return offdiag_tile() + kPanel * kPanel; }
+    __host__ __device__ constexpr int ed() const { return mix() + (mix_scratch ? kMixLdsFloats : 0); }
+    __host__ __device__ constexpr int s() const { return ed() + 2 * kPanel; }
+    __host__ __device__ constexpr int total_floats() const { return mirror ? s() + qcap : ed(); }
+};
 constexpr int kMaxMixtureK = 64;    // generic mixture kernel (estep_generic.h): one lane per component
 constexpr int kGridModels = 32;     // batched grid kernel (estep_grid_mfma.h): models per launch (one 32-row MFMA tile)
 // ... its resident form: 6 owner waves x 2 tiles of 128 columns in accumulator registers = blocks of up to 1 536 SNPs

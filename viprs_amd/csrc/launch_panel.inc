@@ -83,10 +83,9 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
         S.qcap[c] = 0;
         if (end > begin) {
             const int max_b = P->dense_h[begin].size;      // descending order
-            // (the chain's off-diagonal tile is staged in LDS for every model and form: panel_lds_floats(qcap, true))
+            // (the layout the kernel carves: PanelLds, kernels_common.h)
             auto lds_bytes = [&](int qcap) {
-                return (size_t)(panel_lds_floats(qcap, true) + (model == kPanelMixture ? kMixLdsFloats : 0) +
-                                (mirror ? panel_mirror_lds_floats(qcap) : 0)) * sizeof(float);
+                return (size_t)PanelLds(qcap, model == kPanelMixture, mirror).total_floats() * sizeof(float);
             };
             for (;;) {
                 S.qcap[c] = (max_b + kPanel - 1) / kPanel * kPanel + kStrip;

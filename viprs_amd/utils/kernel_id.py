@@ -6,9 +6,9 @@ import os
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 _COMMON = ("kernels_common.h", "device_math.h")
 FAMILIES = {
-    "panel": ("estep_panel.h", "launch_panel.inc"),
+    "panel": ("estep_panel.h", "panel_loads.h", "panel_models.h", "launch_panel.inc"),
     "grid": ("estep_grid_mfma.h", "launch_grid.inc"),
-    "tile_f64": ("estep_tile.h", "launch_tile_f64.inc"),
+    "tile_f64": ("estep_tile.h", "panel_loads.h", "launch_tile_f64.inc"),
 }
 
 
