@@ -472,6 +472,53 @@ int viprs_plan_solve_ridge(viprs_plan* plan, int float_dtype, const void* b_host
                            int32_t* block_iters, double* block_relres, int32_t* block_status /* each nullable */);
 int viprs_plan_last_solve_ms(viprs_plan* plan, double* total_ms, int* iterations);
 
+/* ---- extremal eigenvalues: one Lanczos recurrence per LD block ----------------------------------------------------------
+ * The smallest and the largest eigenvalue of A = unit diagonal + dq_scale * stored off-diagonal entries -- exactly the matrix
+ * of viprs_plan_dot(..., include_diagonal = 1) -- independently for every LD block of the plan (blocks as
+ * viprs_plan_get_blocks lists them, SNP order).  What `lambda_min='infer'` needs (viprs/model/VIPRS.py:174-191 asks the LD
+ * matrix for get_lambda_min(min_max_ratio), which magenpy answers from extremal eigenvalues it computed per block with ARPACK
+ * when the store was built); here every block has its own scalars, its own stopping decision and its own iteration count,
+ * and all blocks advance in lock step: one LD product and one fused kernel per iteration on the plan's stream.
+ *   start      a function of the index i inside the block only: h = the splitmix64 finaliser of (i + 1) * 0x9E3779B97F4A7C15
+ *              (mod 2^64), u_i = (h >> 40) * 2^-24 - 0.5 + 2^-25 (an odd multiple of 2^-25: exact in float32, never zero),
+ *              v = fl(u / ||u||).  Not a constant vector: AR(1) blocks are centrosymmetric and the eigenvector of their
+ *              smallest eigenvalue is antisymmetric for even sizes -- a symmetric start vector never sees it
+ *   per block  iteration k = 1, 2, ... (beta_1 = 0): w = A v - fl(beta_k) v_prev, alpha_k = v.w, w -= fl(alpha_k) v,
+ *              beta_{k+1} = ||w||, v_prev <- v, v <- fl(w / beta_{k+1})
+ *   no reorthogonalisation: the extremal Ritz values converge without it, the ghost copies that the loss of orthogonality
+ *              brings appear at eigenvalues that have already converged and do no harm at the two ends, and the residual
+ *              estimate below stays valid to O(eps ||A||) (Paige 1980)
+ *   precision  vectors and the product in the state precision `float_dtype`; every scalar and every dot product in double
+ *   order      dot products in the order of the ridge solve above: a function of the block's size alone; no floating-point
+ *              atomics.  A block's result does not depend on its place in the plan, on the other blocks or on timing; two
+ *              calls give identical bits
+ *   stopping   at k = 1, 2, 4, 8, ... and at max_iter the host takes the extreme Ritz pairs (theta, s) of the tridiagonal
+ *              T_k (diagonal alpha_1..k, off-diagonal beta_2..k) by the implicit QL iteration, carrying only the last row
+ *              of the eigenvector matrix (O(k^2) operations, O(k) memory).  beta_{k+1} |s_k| is the residual norm of the
+ *              Ritz vector, an upper bound of the distance from theta to the nearest eigenvalue of A.  A block stops when
+ *              both bounds are <= rtol * max(|theta_min|, |theta_max|), or when beta_{k+1} == 0.  k reaching the block's
+ *              size does NOT stop it: in finite precision the Ritz values at k = size are not the eigenvalues.  A block
+ *              whose status is final is frozen: later launches leave it unchanged
+ *   outputs    (each may be NULL) one entry per block: lam_min / lam_max, resid_min / resid_max (the two bounds, absolute),
+ *              iters, status: 0 converged, 1 stopped at max_iter (the Ritz values and bounds of T_max_iter are returned).
+ *              A 1-SNP block gives 1, 1, 0, 0 after 1 iteration
+ * viprs_plan_set_active_blocks does NOT filter the computation.  The workspace (three vectors, 16 * max_iter bytes per block)
+ * lives on the plan and is reused.  The dense blocks of the upper form are read in whichever storage the last sweep left
+ * them, as by the product.
+ * Bad dtype code, rtol <= 0, max_iter < 1, a null plan: VIPRS_EINVAL before any launch, outputs untouched.  An empty plan
+ * returns VIPRS_OK.
+ *   viprs_plan_last_spectrum_ms  HIP-event time from the first to the last kernel of the last call on this plan (the checks
+ *                                of the stopping rule included), the iterations it launched, and (nullable) the host's
+ *                                time inside those checks
+ *   viprs_tridiagonal_extremes   the stopping rule's host routine on its own, no device involved: diagonal alpha[0..k-1],
+ *                                off-diagonal beta[0..k-2]; out = {theta_min, theta_max, |s_k| of theta_min, |s_k| of
+ *                                theta_max}.  k < 1 or a null pointer: VIPRS_EINVAL */
+int viprs_plan_extremal_eigenvalues(viprs_plan* plan, int float_dtype, double dq_scale, double rtol, int max_iter,
+                                    double* lam_min, double* lam_max, double* resid_min, double* resid_max,
+                                    int32_t* block_iters, int32_t* block_status /* each nullable */);
+int viprs_plan_last_spectrum_ms(viprs_plan* plan, double* total_ms, int* iterations, double* host_ms /* nullable */);
+int viprs_tridiagonal_extremes(int k, const double* alpha, const double* beta, double* out);
+
 /* ---- measurement support: synthetic LD generated on the device (bench.py, tests) --------------
  * The "longrange" LD blocks of viprs_amd/utils/synthetic.py (the workload of BASELINE.json's configs, SURVEY.md 8d: the
  * reference gets its LD from magenpy stores, VIPRS.py:151-172, none of which exists here) written straight into a plan's

@@ -91,6 +91,23 @@ struct RidgeWork {
     int iterations = 0;                            // iterations the last solve launched
 };
 
+// extremal eigenvalues (abi_spectrum.hip, lanczos.h): the workspace of a plan, allocated by its first call and reused
+struct SpectrumWork {
+    bool built = false;
+    DevBuf<char> d_blocks;                         // RidgeBlock per LD block, SNP order
+    DevBuf<double> d_beta;                         // beta_k of the iteration to come, per block
+    DevBuf<int32_t> d_status, d_iters;             // per block
+    DevBuf<int32_t> d_live;                        // blocks still running
+    size_t vec_bytes = 0;                          // capacity of each vector below
+    DevBuf<char> d_vec[3];                         // v, v_prev (w while a step runs), A v
+    size_t coef_cap = 0;                           // capacity of each array below (doubles)
+    DevBuf<double> d_alpha, d_betas;               // alpha_k / beta_{k+1} at [block * max_iter + k - 1]
+    DevEvent ev[2];
+    bool timed = false;
+    int iterations = 0;                            // iterations the last call launched
+    double host_ms = 0.0;                          // host time of its checks (downloads + tridiagonal eigenproblems)
+};
+
 }  // namespace viprs
 
 struct viprs_state;
@@ -181,6 +198,7 @@ struct viprs_plan {
     bool dot_timed = false;
     bool unmirrored_wanted = false;                // the last launch that asked for a storage of the upper form wanted the zero lower triangle
     viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
+    viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
 
     ~viprs_plan();
 };

@@ -22,6 +22,7 @@ class LDArrays:
         self.stored_dtype = np.dtype(stored_dtype if stored_dtype is not None else any_form[2].dtype)
         self.dq_scale = float(dq_scale)
         self._lambda_min = lambda_min
+        self._extremal = None
 
     class _Loaded:
         def __init__(self, lb, ip, data):
@@ -38,8 +39,21 @@ class LDArrays:
                 else data.astype(dtype)
         return LDArrays._Loaded(lb, ip, data)
 
-    def get_lambda_min(self, min_max_ratio=1e-3):
-        return self._lambda_min
+    # which candidate formula `get_lambda_min` applies to the extremes for a min / max ratio > 0 (None: it refuses);
+    # see viprs_amd.stats.spectrum.lambda_min_from_extremes
+    lambda_min_formula = None
+
+    def set_extremal(self, lam_min, lam_max):
+        """The extremal eigenvalues of this LD matrix (`viprs_amd.stats.spectrum.annotate_spectrum` computes them on the
+        device): from now on `get_lambda_min` answers from them."""
+        self._extremal = (float(lam_min), float(lam_max))
+
+    def get_lambda_min(self, min_max_ratio=1e-3, formula=None):
+        if self._extremal is None:
+            return self._lambda_min
+        from .stats.spectrum import lambda_min_from_extremes
+        return lambda_min_from_extremes(*self._extremal, min_max_ratio, formula or self.lambda_min_formula,
+                                        where="LDArrays")
 
 
 class SumstatsArrays:

@@ -40,6 +40,8 @@ import zlib
 
 import numpy as np
 
+from ..stats.spectrum import UnpinnedLambdaMinError, lambda_min_from_extremes  # noqa: F401  (the error's old home)
+
 BLOSC_MIN_BUFFERSIZE = 128
 BLOSC_MAX_SPLITS = 16
 _CODEC_NAME = {0: "blosclz", 1: "lz4", 2: "snappy", 3: "zlib", 4: "zstd"}
@@ -460,23 +462,7 @@ class ZarrLDMatrix:
         lam_min, lam_max = pick(ext, "min", "Min"), pick(ext, "max", "Max")
         if lam_min is None:
             return 0.0
-        r = float(min_max_ratio or 0.0)
-        if r > 0.0 and lam_max is not None:
-            formula = formula or self.lambda_min_formula
-            if formula not in ("one_plus_r", "one_minus_r"):
-                raise UnpinnedLambdaMinError(
-                    f"{self.path}: the store carries extremal eigenvalues (min {lam_min}, max {lam_max}) but the formula "
-                    "magenpy's LDMatrix.get_lambda_min(min_max_ratio) applies to them could not be verified (magenpy is "
-                    "not available where this reader was written).  Pass a numeric lambda_min to VIPRS(...), or choose "
-                    "ZarrLDMatrix.lambda_min_formula = 'one_plus_r' | 'one_minus_r' (tools/check_store.py tells which one "
-                    "a magenpy installation agrees with).")
-            den = 1.0 + r if formula == "one_plus_r" else 1.0 - r
-            return max((r * lam_max - lam_min) / den, 0.0)
-        return abs(min(lam_min, 0.0))
-
-
-class UnpinnedLambdaMinError(NotImplementedError):
-    """`lambda_min='infer'` on a store with spectral attributes: the formula is unverified (ZarrLDMatrix.get_lambda_min)."""
+        return lambda_min_from_extremes(lam_min, lam_max, min_max_ratio, formula or self.lambda_min_formula, where=self.path)
 
 
 def write_ld_store(path, ld_indptr, ld_data, attrs=None, chunks=None, cname="zstd", clevel=5, shuffle=1,

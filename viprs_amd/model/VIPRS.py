@@ -115,6 +115,13 @@ class VIPRS:
             warnings.warn("math_mode='fast' has no kernels for " + ("float_precision='float64'" if self._T == np.float64 else
                           f"mixtures of {self.K} components (> 8)") + ": this model runs in EXACT arithmetic", stacklevel=2)
         self._e_step_fn = e_step_fn
+        # lambda_min='compute': the extremal eigenvalues of the LD this model holds, by Lanczos on its device
+        compute_lambda = isinstance(lambda_min, str) and lambda_min == "compute"
+        if compute_lambda and e_step_fn is not None:
+            raise RuntimeError("lambda_min='compute' needs a HIP device: the Lanczos recurrence has no CPU fallback")
+        if compute_lambda and self.comm.world_size > 1:
+            raise NotImplementedError("lambda_min='compute' runs on one rank only (world_size > 1: annotate the LD "
+                                      "matrices with viprs_amd.stats.spectrum.annotate_spectrum and use 'infer')")
 
         # ---- inputs + LD: load, shard at LD-block granularity, then make device-resident ---------
         # (BayesPRSModel.py:118-142, VIPRS.py:151-191).  With several ranks every LD block -- the
@@ -152,6 +159,8 @@ class VIPRS:
                 self.lambda_min = 0.0
             elif _is_numeric(lambda_min):
                 self.lambda_min = lambda_min
+            elif compute_lambda:
+                pass                             # (below, once the LD is on the device)
             else:                                # 'infer': the reference keeps the LAST chromosome's value (:186-191)
                 try:
                     self.lambda_min = ld_mat.get_lambda_min(min_max_ratio=1e-3)
@@ -249,6 +258,8 @@ class VIPRS:
                 if self._resident:
                     for c in self.chromosomes:
                         self._dstate[c].set_n_per_snp(self.n_per_snp[c])
+            if compute_lambda:
+                self._compute_lambda_min()
         else:
             self._resident = self._merged = False
             if self._expanded:          # test hook: the host model of the device-side expansion
@@ -271,6 +282,21 @@ class VIPRS:
         self._sums = None
         self._sums_valid = False
         self._max_eta_diff = 0.0
+
+    def _compute_lambda_min(self):
+        """lambda_min='compute': |min(smallest eigenvalue, 0)| of every chromosome's LD, from the extremal eigenvalues of
+        its LD blocks (`LDPlan.extremal_eigenvalues` on the plans of this model: the matrix the E-step multiplies with, in
+        the model's precision).  No min / max ratio, hence none of the unpinned formulas.  `lambda_min` itself is the LAST
+        chromosome's value, as with 'infer' (the reference, VIPRS.py:186-191); `lambda_min_computed` keeps every
+        chromosome's, `spectrum` what they were derived from."""
+        from ..stats.spectrum import lambda_min_from_extremes, plan_spectrum
+        kw = dict(dq_scale=self.dequantize_scale, float_precision=self.float_precision)
+        if self._merged:
+            self.spectrum = plan_spectrum(self._plans["*"], self._seg, **kw)
+        else:
+            self.spectrum = {c: plan_spectrum(self._plans[c], **kw)[None] for c in self.chromosomes}
+        self.lambda_min_computed = {c: lambda_min_from_extremes(s["min"], s["max"]) for c, s in self.spectrum.items()}
+        self.lambda_min = self.lambda_min_computed[sorted(self.lambda_min_computed)[-1]]
 
     # ---- sizes ------------------------------------------------------------------------------------
     @property

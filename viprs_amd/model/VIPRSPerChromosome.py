@@ -46,8 +46,10 @@ class PerChromosomeGroups:
 
     def __init__(self, gdl, lambda_min=None, **kwargs):
         """Arguments of the model class; ``lambda_min='infer'`` gives every chromosome the value of ITS LD matrix (each of the
-        reference's per-chromosome models infers its own, VIPRS.py:186-191)."""
-        infer = lambda_min is not None and not _is_numeric(lambda_min)
+        reference's per-chromosome models infers its own, VIPRS.py:186-191); ``lambda_min='compute'`` the value computed on
+        the device from ITS LD blocks."""
+        compute = isinstance(lambda_min, str) and lambda_min == "compute"
+        infer = lambda_min is not None and not _is_numeric(lambda_min) and not compute
         super().__init__(gdl, lambda_min=None if infer else lambda_min, **kwargs)
         self.groups = sorted(self._all_shapes)                     # one model per chromosome of the data loader
         self._gindex = {c: g for g, c in enumerate(self.groups)}
@@ -57,6 +59,9 @@ class PerChromosomeGroups:
         if infer:
             ld = gdl.get_ld_matrices()
             self._lambda_group = [ld[c].get_lambda_min(min_max_ratio=1e-3) for c in self.groups]
+        elif compute:
+            self._lambda_group = [self.lambda_min_computed[c] for c in self.groups]
+            self.lambda_min = 0.0                                  # (as with 'infer': the groups carry the values)
         else:
             self._lambda_group = [self.lambda_min] * len(self.groups)
         self.optim_results = {}

@@ -75,6 +75,34 @@ class RidgeInfo:
                 f"max_iterations={int(self.iterations.max(initial=0))}, ms={self.ms:.3f})")
 
 
+class SpectrumInfo:
+    """What `LDPlan.extremal_eigenvalues` reports, per LD block (SNP order): `lambda_min` / `lambda_max` (the extreme Ritz
+    values), `resid_min` / `resid_max` (absolute bounds of their distance to the nearest eigenvalue), `iterations`, `status`
+    (0 converged, 1 stopped at maxiter); `converged`: no block stopped at maxiter; `ms`: time of the call on the device's
+    clock, `host_ms`: the part the host spent on the tridiagonal eigenproblems."""
+    CONVERGED, MAXITER = 0, 1
+
+    def __init__(self, lambda_min, lambda_max, resid_min, resid_max, iterations, status, ms=0.0, host_ms=0.0):
+        self.lambda_min = np.asarray(lambda_min, dtype=np.float64)
+        self.lambda_max = np.asarray(lambda_max, dtype=np.float64)
+        self.resid_min = np.asarray(resid_min, dtype=np.float64)
+        self.resid_max = np.asarray(resid_max, dtype=np.float64)
+        self.iterations = np.asarray(iterations, dtype=np.int32)
+        self.status = np.asarray(status, dtype=np.int32)
+        self.ms = float(ms)
+        self.host_ms = float(host_ms)
+
+    @property
+    def converged(self):
+        return bool(np.all(self.status == self.CONVERGED))
+
+    def __repr__(self):
+        lo = float(self.lambda_min.min()) if self.lambda_min.size else float("nan")
+        hi = float(self.lambda_max.max()) if self.lambda_max.size else float("nan")
+        return (f"SpectrumInfo(blocks={self.status.shape[0]}, min={lo:.6g}, max={hi:.6g}, converged={self.converged}, "
+                f"max_iterations={int(self.iterations.max(initial=0))}, ms={self.ms:.3f})")
+
+
 class LDPlan:
     """Device-resident LD matrix of one chromosome (or any set of LD blocks)."""
 
@@ -322,6 +350,37 @@ class LDPlan:
         ms, n = ctypes.c_double(0.0), ctypes.c_int(0)
         L.check(L.lib.viprs_plan_last_solve_ms(self.handle, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+    # -- extremal eigenvalues ---------------------------------------------------------------------
+    def extremal_eigenvalues(self, dq_scale=1.0, rtol=None, maxiter=None, float_precision="float32"):
+        """Smallest and largest eigenvalue of every LD block by one Lanczos recurrence per block, all blocks in lock step
+        (`viprs_plan_extremal_eigenvalues`; what magenpy computes with ARPACK when it builds an LD store).  `R` as in `dot`
+        with the diagonal; the recurrence's vectors are in `float_precision`.  Defaults: ``rtol`` 1e-4 (a tenth of the
+        ``min_max_ratio`` 1e-3 the models resolve), ``maxiter`` 2048.  Returns a `SpectrumInfo`.  `set_active_blocks` does
+        not filter the computation."""
+        dt = np.dtype(float_precision)
+        if dt not in _FLOAT_CODE:
+            raise ValueError(f"float_precision: expected float32 or float64, got {float_precision}")
+        rtol = 1e-4 if rtol is None else float(rtol)
+        maxiter = 2048 if maxiter is None else int(maxiter)
+        n_blocks = self.n_blocks
+        lo, hi = np.zeros(n_blocks), np.zeros(n_blocks)
+        r_lo, r_hi = np.zeros(n_blocks), np.zeros(n_blocks)
+        iters = np.zeros(n_blocks, dtype=np.int32)
+        status = np.zeros(n_blocks, dtype=np.int32)
+        L.check(L.lib.viprs_plan_extremal_eigenvalues(self.handle, _FLOAT_CODE[dt], float(dq_scale), rtol, maxiter,
+                                                      _ptr(lo), _ptr(hi), _ptr(r_lo), _ptr(r_hi), _ptr(iters),
+                                                      _ptr(status)))
+        ms, _, host_ms = self.last_spectrum_ms() if self.m else (0.0, 0, 0.0)
+        return SpectrumInfo(lo, hi, r_lo, r_hi, iters, status, ms, host_ms)
+
+    def last_spectrum_ms(self):
+        """``(ms, iterations, host_ms)`` of the last `extremal_eigenvalues` on this plan: HIP-event time from its first to
+        its last kernel (the checks of the stopping rule included), the iterations it launched, and the host's time inside
+        those checks."""
+        ms, n, host = ctypes.c_double(0.0), ctypes.c_int(0), ctypes.c_double(0.0)
+        L.check(L.lib.viprs_plan_last_spectrum_ms(self.handle, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(host)))
+        return ms.value, n.value, host.value
 
     # -- one-shot host-buffer E-steps (drop-ins for the Cython entry points) -------------------
     def e_step(self, std_beta, var_gamma, var_mu, eta, q, eta_diff, u_logs, sqrt_half_var_tau, mu_mult,
