@@ -437,6 +437,41 @@ int viprs_plan_dot(viprs_plan* plan, int float_dtype, int n_cols, const void* b_
 int viprs_state_dot(viprs_state* state, int field, double dq_scale, int include_diagonal, void* y_host);
 int viprs_plan_last_dot_ms(viprs_plan* plan, double* ms);
 
+/* ---- LD scores: l[j, g] = sum_k A[k, g] r_jk^2 over EVERY block of a plan ----------------------------------------------
+ * What the reference gets from magenpy's LD layer (`compute_ld_scores`, with `annotation_matrix` for the stratified
+ * scores) and feeds to `magenpy.stats.h2.ldsc.simple_ldsc` (viprs/model/LDPredInf.py:32-33, VIPRS.py:279-292).  magenpy is
+ * not part of the reference tree: the definition below is this library's own, stated in full.
+ * `a_host` and `scores_host` are (m, n_cols), column-major, in the state precision `float_dtype`; `a_host == NULL` means ONE
+ * column of ones (n_cols must be 1): that path loads no weights at all.  `corr_host` is (m,) doubles or NULL.
+ * Per row j and column g, over the OFF-DIAGONAL entries (j, i) of row j -- the entry set of viprs_plan_dot: a stored zero
+ * is an entry, the gaps of a window and the diagonal are not --
+ *   S2[j, g] = sum p_ji A[i, g]     x = T(stored element) (exact for int8 / int16 / fp32 LD), p = fl(x x); every term enters
+ *                                   by ONE fused multiply-add fma(p, A[i, g], acc) in the state precision T
+ *   S0[j, g] = sum A[i, g]          plain additions into a second accumulator
+ * both in THE ORDER of viprs_plan_dot: entry e of the row's window to accumulator e % V of lane (e / V) % 64 in ascending
+ * e, then the binary tree over V, then the xor butterfly over the 64 lanes; the diagonal and the gaps add an exact zero to
+ * both.  (Unit weights: S2 = sum p in that order, S0 = the number of entries of the row.)  Then, every operation
+ * separately rounded in T, no contraction:
+ *   d = fl(dq_scale);  d2 = fl(d d);  U = fl(d2 S2)
+ *   corr_host == NULL:  score = fl(U + A[j, g])
+ *   corr_host != NULL:  c = fl(corr[j]);  score = fl(fl(U + fl(c fl(U - S0))) + A[j, g])
+ * The corrected form is sum_k a_k (r^2 - (1 - r^2) c) with c_j = 1 / (n_LD - 2), the adjusted r^2 of LD-score regression,
+ * rearranged so that the two sums suffice; the diagonal contributes A[j, g] in both forms (r_jj = 1, its correction is 0).
+ * int16 squares above 2^24 round in a float32 state: p = fl(x x) is the definition.
+ * ROUNDING.  Every S2 is within eps_T (D(L) + 1) sum p |A| of the exact sum of the squares (D(L) as defined for the
+ * product; the + 1 is the rounding of p), every S0 within eps_T D(L) sum |A| of its exact sum.  A column's result depends
+ * on nothing but the row's entries and that column: not on the other columns or their number, not on which storage of the
+ * upper form the dense blocks are in, not on the active blocks (viprs_plan_set_active_blocks does NOT filter the call), not
+ * on timing.  Two calls give identical bits.  No LDS, no atomics.
+ * On the plan's stream, synchronous; an upper-form plan that has not been swept yet is mirrored once, as for the product.
+ * Bad dtype code, n_cols < 1, a_host == NULL with n_cols != 1, a null plan or a null output: VIPRS_EINVAL before any launch,
+ * `scores_host` untouched.  An empty plan returns VIPRS_OK.
+ *   viprs_plan_last_ld_score_ms  HIP-event time of the kernels of the last call on this plan; the sweeps' timing ring never
+ *                                sees the call */
+int viprs_plan_ld_scores(viprs_plan* plan, int float_dtype, int n_cols, const void* a_host, const double* corr_host,
+                         void* scores_host, double dq_scale);
+int viprs_plan_last_ld_score_ms(viprs_plan* plan, double* ms);
+
 /* ---- ridge solve: the LDPred-inf estimate, one MINRES per LD block -----------------------------------------------------
  * Solves (R + diag(shift)) x = b, independently for every LD block of the plan (blocks as viprs_plan_get_blocks lists
  * them, SNP order), by MINRES (Paige & Saunders 1975), x0 = 0 or the caller's. R = unit diagonal + dq_scale * stored

@@ -4,11 +4,9 @@
 
 using namespace viprs;
 
-namespace {
-
 // Tables of the product: every block of the plan (the active-block filter of the sweeps does not apply), one work item per
 // row, in the order of the plan's full block lists (the dense blocks as the schedule sorted them, then the windowed ones).
-int build_dot_tables(viprs_plan* P) {
+int viprs::build_dot_tables(viprs_plan* P) {
     if (P->dot_built) return VIPRS_OK;
     std::vector<BlockDesc> blocks(P->dense_all_h);
     blocks.insert(blocks.end(), P->ragged_all_h.begin(), P->ragged_all_h.end());
@@ -55,8 +53,6 @@ int build_dot_tables(viprs_plan* P) {
     P->dot_built = true;
     return VIPRS_OK;
 }
-
-}  // namespace
 
 // the kernels of one product on the plan's stream, between the product's own two events (internal.h: the ridge solve calls it too)
 int viprs::enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal) {

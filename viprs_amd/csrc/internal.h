@@ -197,6 +197,11 @@ struct viprs_plan {
     hipEvent_t ev_dot[2] = {nullptr, nullptr};
     bool dot_timed = false;
     bool unmirrored_wanted = false;                // the last launch that asked for a storage of the upper form wanted the zero lower triangle
+    // LD scores (abi_ld_score.hip, ld_score.h): the product's tables; its own staging and event pair
+    viprs::DevBuf<char> d_score_a, d_score_y;
+    viprs::DevBuf<double> d_score_corr;
+    viprs::DevEvent ev_score[2];
+    bool score_timed = false;
     viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
     viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
 
@@ -277,6 +282,8 @@ int team_launch_done(viprs_plan* P);
 // after a synchronisation point: did a team hand-off give up (bounded spin)?
 int check_device_error(viprs_plan* P);
 
+// abi_dot.hip: the tables of the product (every block of the plan, one work item per row), built once per plan
+int build_dot_tables(viprs_plan* P);
 // abi_dot.hip: the kernels of one LD product on the plan's stream (device pointers, (m, n_cols) column-major), between the
 // product's own two events; nothing is synchronised
 int enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal);
@@ -305,5 +312,8 @@ template <typename U> int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A);
 // LD product Y = dq_scale (R - diag) B (+ B) over every block of the plan (ld_dot.h); device pointers, (m, n_cols) column-major
 template <typename U> int launch_ld_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale,
                                         int include_diagonal);
+// LD scores over every block of the plan (ld_score.h); device pointers, dA null: unit weights, dCorr null: no correction
+template <typename U> int launch_ld_score(viprs_plan* P, int float_dtype, int n_cols, const void* dA, const double* dCorr,
+                                          void* dY, double dq_scale);
 
 }  // namespace viprs

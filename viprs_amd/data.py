@@ -14,7 +14,7 @@ class LDArrays:
     """LD of one chromosome in the contiguous-window layout.  Holds the
     symmetric and/or the upper-triangular form; ``load`` hands out the one asked for."""
 
-    def __init__(self, symmetric=None, upper=None, stored_dtype=None, dq_scale=1.0, lambda_min=0.0):
+    def __init__(self, symmetric=None, upper=None, stored_dtype=None, dq_scale=1.0, lambda_min=0.0, sample_size=None):
         if symmetric is None and upper is None:
             raise ValueError("need at least one LD form")
         self._forms = {True: symmetric, False: upper}      # key: return_symmetric
@@ -23,6 +23,8 @@ class LDArrays:
         self.dq_scale = float(dq_scale)
         self._lambda_min = lambda_min
         self._extremal = None
+        self.sample_size = sample_size                      # of the panel the LD was estimated from (None: unknown)
+        self._ld_score = None
 
     class _Loaded:
         def __init__(self, lb, ip, data):
@@ -48,6 +50,18 @@ class LDArrays:
         device): from now on `get_lambda_min` answers from them."""
         self._extremal = (float(lam_min), float(lam_max))
 
+    def set_ld_score(self, ld_score):
+        """The per-SNP LD scores of this matrix (`viprs_amd.stats.ldsc.annotate_ld_scores` computes them on the device):
+        from now on `ld_score` answers."""
+        self._ld_score = np.asarray(ld_score, dtype=np.float64)
+
+    @property
+    def ld_score(self):
+        if self._ld_score is None:
+            raise ValueError("LDArrays: no LD scores attached; compute them with "
+                             "viprs_amd.stats.ldsc.annotate_ld_scores(gdl) (or set_ld_score)")
+        return self._ld_score
+
     def get_lambda_min(self, min_max_ratio=1e-3, formula=None):
         if self._extremal is None:
             return self._lambda_min
@@ -57,12 +71,20 @@ class LDArrays:
 
 
 class SumstatsArrays:
-    def __init__(self, std_beta, n_per_snp):
+    def __init__(self, std_beta, n_per_snp, chisq=None):
         self._std_beta = np.asarray(std_beta)
         self.n_per_snp = np.asarray(n_per_snp, dtype=np.float64)
+        self._chisq = None if chisq is None else np.asarray(chisq, dtype=np.float64)
 
     def get_snp_pseudo_corr(self):
         return self._std_beta
+
+    def get_chisq_statistic(self):
+        """The association statistic per SNP: the one the caller gave (`chisq=`), else N_j beta_hat_j^2 from the
+        standardised effects the models use."""
+        if self._chisq is not None:
+            return self._chisq
+        return self.n_per_snp * np.asarray(self._std_beta, dtype=np.float64) ** 2
 
 
 class ArrayDataLoader:
@@ -93,10 +115,11 @@ class ArrayDataLoader:
 
     @classmethod
     def synthetic(cls, chrom_sizes, ld_dtype=np.float32, seed=7209, n=1e5, forms=("symmetric", "upper"), h2=0.2,
-                  kind="ar1"):
+                  kind="ar1", ld_sample_size=None):
         """Synthetic block LD (`kind`: "ar1" | "longrange" | "sample") + simulated summary statistics
         (viprs_amd.utils.synthetic) per chromosome; the total heritability `h2` is shared between the
-        chromosomes in proportion to their SNP counts."""
+        chromosomes in proportion to their SNP counts.  `ld_sample_size`: the size of the panel the LD stands for
+        (`LDArrays.sample_size`, what corrected LD scores need); None: unknown, as for LD given as bare arrays."""
         m_total = float(sum(int(np.sum(s)) for s in chrom_sizes.values()))
         from .utils import synthetic as syn
         ld, ss = {}, {}
@@ -108,7 +131,7 @@ class ArrayDataLoader:
             ld[chrom] = LDArrays(
                 symmetric=(sym.ld_left_bound, sym.ld_indptr, sym.ld_data) if "symmetric" in forms else None,
                 upper=(up.ld_left_bound, up.ld_indptr, up.ld_data) if up is not None else None,
-                stored_dtype=ld_dtype, dq_scale=sym.dq_scale)
+                stored_dtype=ld_dtype, dq_scale=sym.dq_scale, sample_size=ld_sample_size)
             ss[chrom] = SumstatsArrays(s.std_beta, s.n_per_snp)
         return cls(ld, ss, n=n)
 

@@ -403,6 +403,23 @@ class ZarrLDMatrix:
     def metadata(self, name):
         return ZarrArray(os.path.join(self.path, "metadata", name)).read()
 
+    _ld_score = None
+
+    def set_ld_score(self, ld_score):
+        """Attach per-SNP LD scores (`viprs_amd.stats.ldsc.annotate_ld_scores`)."""
+        self._ld_score = np.asarray(ld_score, dtype=np.float64)
+
+    @property
+    def ld_score(self):
+        """Per-SNP LD scores: the attached ones, else the store's own per-SNP LD-score metadata array if it has one."""
+        if self._ld_score is not None:
+            return self._ld_score
+        for name in ("ldscore", "LDScore", "ld_score"):
+            if os.path.exists(os.path.join(self.path, "metadata", name, ".zarray")):
+                return np.asarray(self.metadata(name), dtype=np.float64)
+        raise ValueError(f"{self.path}: the store has no per-SNP LD scores; compute them with "
+                         "viprs_amd.stats.ldsc.annotate_ld_scores(gdl) (or set_ld_score)")
+
     class _Loaded:
         def __init__(self, lb, ip, data):
             self.leftmost_idx, self.ld_indptr, self.ld_data = lb, ip, data

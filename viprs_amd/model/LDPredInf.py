@@ -5,11 +5,12 @@ The reference's class (viprs/model/LDPredInf.py) assembles one block-diagonal sp
 system is solved LD block by LD block, all blocks in lock step (``LDPlan.solve_ridge``): the converged solution is the
 same, every block stops on its own residual.
 
-Two deviations from the reference, both on purpose:
+One deviation from the reference, on purpose: the right-hand side is the vector of STANDARDISED marginal effects
+(``get_snp_pseudo_corr()``), as for every model of this package -- the reference passes ``marginal_beta``, which is on the
+scale of ``R`` only for standardised genotypes.
 
-* the right-hand side is the vector of STANDARDISED marginal effects (``get_snp_pseudo_corr()``), as for every model of
-  this package -- the reference passes ``marginal_beta``, which is on the scale of ``R`` only for standardised genotypes;
-* ``h2`` is required: the reference's default, an LD-score regression estimate, lives in magenpy, which is not in the tree.
+``h2=None`` estimates the heritability as the reference does (LDPredInf.py:32-33, ``simple_ldsc``): the LD scores of the
+model's own plan (``LDPlan.ld_scores`` with the sample-size correction), then ``viprs_amd.stats.ldsc``'s estimate.
 
 There is no CPU fallback: without ``libviprs_hip.so`` and a GPU ``fit()`` raises.  (``solve_fn`` lets the CPU tests drive
 this host logic with the host model of the solver; it is never set by the package itself.)
@@ -25,23 +26,23 @@ from ._ld_loading import dequantize_scale, ld_load_dtype, load_ld_arrays
 class LDPredInf:
 
     def __init__(self, gdl, h2=None, float_precision="float32", low_memory=True, dequantize_on_the_fly=False,
-                 device=None, solve_fn=None, comm=None):
+                 device=None, solve_fn=None, comm=None, score_fn=None):
         """:param gdl: the data loader (summary statistics and LD matrices per chromosome).
-        :param h2: heritability of the trait (a number in (0, 1]).
+        :param h2: heritability of the trait (a number in (0, 1]); None: the LD-score regression estimate
+            (`viprs_amd.stats.ldsc.simple_ldsc` with corrected LD scores; needs the LD objects' ``sample_size``).
         :param float_precision: precision of the solve, 'float32' or 'float64'.
         :param low_memory: load the upper-triangular form of the LD matrices.
         :param dequantize_on_the_fly: keep integer LD in its stored dtype on the device.
         :param device: HIP device index (default 0).
         :param solve_fn: test hook -- a callable ``(lb, ip, data, low_memory, b, shift, dq_scale, rtol, maxiter, x0) ->
             (x, info)`` that replaces the device solve.
+        :param score_fn: test hook -- a callable with `viprs_amd.stats.ldsc.ld_scores_host`'s signature that computes the
+            LD scores of ``h2=None`` (the default on the host path: `ld_scores_host` itself).
         """
         if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
             raise AssertionError("The data loader must contain summary statistics and LD matrices.")
         if comm is not None and comm.world_size > 1:
             raise NotImplementedError("LDPredInf runs on one rank only (world_size > 1: the solve is not sharded)")
-        if h2 is None:
-            raise ValueError("LDPredInf needs h2: the reference's default (LD-score regression, "
-                             "magenpy.stats.h2.ldsc.simple_ldsc) needs magenpy, which is not in the tree")
         self.gdl = gdl
         self.h2 = h2
         self.float_precision = float_precision
@@ -55,6 +56,14 @@ class LDPredInf:
         chroms = self.chromosomes
         ld_data, ld_indptr, ld_left_bound = {}, {}, {}
         self.std_beta = {}
+        corr = None
+        if h2 is None:
+            from ..stats.ldsc import ld_correction
+            try:
+                corr = np.concatenate([ld_correction(ld_mats[c], self.shapes[c], where=f"chromosome {c}") for c in chroms])
+            except ValueError as e:
+                raise ValueError("LDPredInf(h2=None) estimates h2 by LD-score regression (the reference's default, "
+                                 f"magenpy.stats.h2.ldsc.simple_ldsc) -- {e}  Or pass h2.") from e
         for c in chroms:
             dtype, dequantize_on_the_fly = ld_load_dtype(ld_mats[c], dequantize_on_the_fly, float_precision)
             lop, _ = load_ld_arrays(ld_mats[c], self.low_memory, dtype, expand_ld_on_device=False)
@@ -74,9 +83,28 @@ class LDPredInf:
             self._plan = LDPlan(lb, ip, data, self.low_memory, device=self.device)
         else:
             self._ld = (lb, ip, data)
+        if h2 is None:
+            self.h2 = self._estimate_h2(lb, ip, data, corr, score_fn)
         self.lam = None
         self.post_mean_beta = None
         self.solve_info = None
+
+    def _estimate_h2(self, lb, ip, data, corr, score_fn):
+        """`simple_ldsc` over the model's own LD: corrected unit-weight scores of its plan (the host path: `score_fn` or
+        `ld_scores_host`), then the estimate over all chromosomes."""
+        from ..stats.ldsc import chisq_statistic, ld_scores_host, ldsc_estimate
+        if self._plan is not None and score_fn is None:
+            scores = self._plan.ld_scores(None, corr, dq_scale=self.dequantize_scale, float_precision=self.float_precision)
+        else:
+            scores = (score_fn or ld_scores_host)(lb, ip, data, self.low_memory, None, corr, self.dequantize_scale)
+        self.ld_score = {c: np.asarray(scores[a:e], dtype=np.float64) for c, (a, e) in self._seg.items()}
+        ss = self.gdl.sumstats_table
+        chroms = self.chromosomes
+        h2 = ldsc_estimate(np.concatenate([chisq_statistic(ss[c]) for c in chroms]), scores,
+                           np.concatenate([np.asarray(ss[c].n_per_snp, dtype=np.float64).ravel() for c in chroms]))
+        if not 0.0 < h2 <= 1.0:
+            raise ValueError(f"LDPredInf(h2=None): the LD-score regression estimate h2 = {h2!r} is not in (0, 1]; pass h2")
+        return h2
 
     @property
     def chromosomes(self):

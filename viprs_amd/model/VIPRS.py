@@ -74,7 +74,7 @@ class VIPRS:
     def __init__(self, gdl, fix_params=None, tracked_params=None, lambda_min=None, float_precision="float32",
                  order="F", low_memory=True, dequantize_on_the_fly=False, threads=1,
                  device=None, comm=None, math_mode="exact", e_step_fn=None, device_resident=True,
-                 merge_chromosomes=True, expand_ld_on_device=None):
+                 merge_chromosomes=True, expand_ld_on_device=None, h2_init=None, score_fn=None):
         """Same arguments as the reference (VIPRS.py:68-77) plus:
 
         :param device: HIP device index (default: ``comm.rank`` modulo the visible devices).
@@ -122,6 +122,15 @@ class VIPRS:
         if compute_lambda and self.comm.world_size > 1:
             raise NotImplementedError("lambda_min='compute' runs on one rank only (world_size > 1: annotate the LD "
                                       "matrices with viprs_amd.stats.spectrum.annotate_spectrum and use 'infer')")
+
+        if not (h2_init is None or _is_numeric(h2_init) or (isinstance(h2_init, str) and h2_init == "ldsc")):
+            raise ValueError(f"h2_init: None, 'ldsc' or a number, got {h2_init!r}")
+        if isinstance(h2_init, str) and self.comm.world_size > 1:
+            raise NotImplementedError("h2_init='ldsc' runs on one rank only (world_size > 1: compute the estimate with "
+                                      "viprs_amd.stats.ldsc.simple_ldsc and pass it as a number)")
+        self.h2_init = h2_init
+        self._score_fn = score_fn
+        self.h2_ldsc = None
 
         # ---- inputs + LD: load, shard at LD-block granularity, then make device-resident ---------
         # (BayesPRSModel.py:118-142, VIPRS.py:151-191).  With several ranks every LD block -- the
@@ -298,6 +307,51 @@ class VIPRS:
         self.lambda_min_computed = {c: lambda_min_from_extremes(s["min"], s["max"]) for c, s in self.spectrum.items()}
         self.lambda_min = self.lambda_min_computed[sorted(self.lambda_min_computed)[-1]]
 
+    _h2_clip = (0.01, 0.99)              # the reference's clip of the LD-score estimate (VIPRS.py:286)
+
+    def _ldsc_h2(self):
+        """h2_init='ldsc': the LD scores of the LD this model holds -- `LDPlan.ld_scores` on its plans, unit weights, in the
+        model's precision; on the host (`score_fn` or `ld_scores_host`) with ``e_step_fn`` or ``score_fn`` -- and the
+        estimates `viprs_amd.stats.ldsc.ldsc_estimate` derives from them: ``h2_ldsc["*"]`` over all chromosomes, as the
+        reference's ``simple_ldsc(gdl)``, and ``h2_ldsc[c]`` of every chromosome on its own.  The sample-size correction
+        applies when every LD object knows its ``sample_size``.  Computed once; ``ld_score`` keeps the scores."""
+        if self.h2_ldsc is not None:
+            return self.h2_ldsc
+        from ..stats.ldsc import chisq_statistic, ld_correction, ld_scores_host, ldsc_estimate
+        ld_mats, ss = self.gdl.get_ld_matrices(), self.gdl.sumstats_table
+        chroms = sorted(self.shapes)
+        corrected = all(getattr(ld_mats[c], "sample_size", None) is not None for c in chroms)
+        corr = {c: ld_correction(ld_mats[c], self.shapes[c], where=f"chromosome {c}") if corrected else None for c in chroms}
+        if self._e_step_fn is None and self._score_fn is None:
+            kw = dict(dq_scale=self.dequantize_scale, float_precision=self.float_precision)
+            if self._merged:
+                flat = self._plans["*"].ld_scores(None, np.concatenate([corr[c] for c in chroms]) if corrected else None, **kw)
+                scores = {c: flat[a:e] for c, (a, e) in self._seg.items()}
+            else:
+                scores = {c: self._plans[c].ld_scores(None, corr[c], **kw) for c in chroms}
+        else:
+            fn = self._score_fn or ld_scores_host
+            upper = bool(self.low_memory) or self._expanded
+            scores = {c: fn(self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c], upper, None, corr[c],
+                            self.dequantize_scale) for c in chroms}
+        self.ld_score = {c: np.asarray(scores[c], dtype=np.float64) for c in chroms}
+        chisq = {c: chisq_statistic(ss[c]) for c in chroms}
+        n = {c: np.asarray(ss[c].n_per_snp, dtype=np.float64).ravel() for c in chroms}
+        est = {c: ldsc_estimate(chisq[c], self.ld_score[c], n[c]) for c in chroms}
+        est["*"] = ldsc_estimate(*(np.concatenate([d[c] for c in chroms]) for d in (chisq, self.ld_score, n)))
+        self.h2_ldsc = est
+        return est
+
+    def _h2_start(self, chrom=None):
+        """The clipped heritability `initialize_theta` starts from (None: the random draw): of the model over all
+        chromosomes, or of chromosome `chrom`'s own model."""
+        if self.h2_init is None:
+            return None
+        h2 = self._ldsc_h2()["*" if chrom is None else chrom] if isinstance(self.h2_init, str) else float(self.h2_init)
+        if not np.isfinite(h2):
+            raise ValueError(f"h2_init={self.h2_init!r}: the heritability estimate is {h2!r}")
+        return float(np.clip(h2, *self._h2_clip))
+
     # ---- sizes ------------------------------------------------------------------------------------
     @property
     def chromosomes(self):
@@ -366,8 +420,10 @@ class VIPRS:
         self._sigma_g = t(0.0)
 
     @staticmethod
-    def _theta_values(th, n_snps):
-        """(pi, sigma_epsilon, tau_beta) of VIPRS.py:260-310 for a model over `n_snps` variants, before the casts."""
+    def _theta_values(th, n_snps, h2_start=None):
+        """(pi, sigma_epsilon, tau_beta) of VIPRS.py:260-310 for a model over `n_snps` variants, before the casts.
+        `h2_start`: a callable giving the heritability to start from where neither sigma_epsilon nor tau_beta is given
+        (None, or a callable returning None: the reference's fallback draw)."""
         if "pi" in th:
             pi = th["pi"]
         else:                                                      # VIPRS.py:260-265
@@ -378,15 +434,17 @@ class VIPRS:
         elif "tau_beta" in th:                                     # :295-300
             tau_beta = th["tau_beta"]
             sigma_epsilon = np.clip(1.0 - pi * n_snps / tau_beta, 1e-4, 1.0 - 1e-4)
-        else:                                                      # :279-292 (no simple_ldsc without magenpy)
-            h2 = np.random.uniform(low=0.01, high=0.1)
+        else:                                                      # :279-292
+            h2 = h2_start() if h2_start is not None else None
+            if h2 is None:
+                h2 = np.random.uniform(low=0.01, high=0.1)
             sigma_epsilon = 1.0 - h2
             tau_beta = pi * n_snps / max(h2, 0.01)
         return pi, sigma_epsilon, tau_beta
 
     def initialize_theta(self, theta_0=None):
         th = self._merge_theta(theta_0)
-        self.pi, self.sigma_epsilon, self.tau_beta = self._theta_values(th, self.n_snps)
+        self.pi, self.sigma_epsilon, self.tau_beta = self._theta_values(th, self.n_snps, self._h2_start)
         self._cast_theta()
 
     def get_pi(self, chrom=None):

@@ -23,6 +23,8 @@ class VIPRSMix(VIPRS):
             self.d = 2 ** np.linspace(-min(K - 1, 7), 0, K).astype(self._T)            # VIPRSMix.py:52
         self.n_per_snp = {c: n[:, None].astype(self._T, order=self.order) for c, n in self.n_per_snp.items()}
 
+    _h2_clip = (1e-3, 1.0 - 1e-3)        # the reference's clip of the LD-score estimate (VIPRSMix.py:134)
+
     def _shape(self, c):
         return (self.shapes[c], self.K)
 
@@ -59,7 +61,10 @@ class VIPRSMix(VIPRS):
             self.tau_beta = th["tau_beta"] * self.d
             self.sigma_epsilon = np.clip(1.0 - (self.n_snps * self.pi / self.tau_beta).sum(), 1e-4, 1.0 - 1e-4)
         else:
-            h2 = np.random.uniform(low=0.001, high=0.999)
+            cur = getattr(self, "_cur", None)                      # (per-chromosome batch: the model that is swapped in)
+            h2 = self._h2_start(None if cur is None else self.groups[cur])
+            if h2 is None:
+                h2 = np.random.uniform(low=0.001, high=0.999)
             self.sigma_epsilon = 1.0 - h2
             self.tau_beta = self.d * (self.n_snps * np.dot(1.0 / self.d, self.pi) / h2)
         self._cast_theta()

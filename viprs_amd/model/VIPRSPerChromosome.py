@@ -119,7 +119,7 @@ class VIPRSPerChromosome(PerChromosomeGroups, VIPRS):
         if isinstance(theta_0, dict) and theta_0 and all(k in self._gindex for k in theta_0):
             t0 = theta_0.get(c)                                    # {chromosome: theta_0}
         th = self._merge_theta(dict(t0) if t0 else None)
-        return self._theta_values(th, int(self._m_group[self._gindex[c]]))
+        return self._theta_values(th, int(self._m_group[self._gindex[c]]), lambda: self._h2_start(c))
 
     def _cast_group_theta(self, raw):
         """The casts of `_cast_theta` for every group; several ranks take rank 0's values (random draws differ)."""

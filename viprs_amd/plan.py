@@ -304,6 +304,47 @@ class LDPlan:
         L.check(L.lib.viprs_plan_last_dot_ms(self.handle, ctypes.byref(ms)))
         return ms.value
 
+    # -- LD scores ----------------------------------------------------------------------------
+    def ld_scores(self, weights=None, correction=None, dq_scale=1.0, float_precision="float32"):
+        """LD scores ``l[j, g] = sum_k A[k, g] r_jk^2`` over every block of the plan (`viprs_plan_ld_scores`; magenpy's
+        ``compute_ld_scores``).  `weights`: None (one column of ones, the unstratified scores; the result is ``(m,)`` in
+        `float_precision`) or an ``(m,)`` / ``(m, G)`` float32 / float64 array of annotations (the result has its shape and
+        dtype).  `correction`: None or ``(m,)`` values ``c_j`` -- every off-diagonal ``r^2`` becomes ``r^2 - (1 - r^2) c_j``
+        (``c = 1 / (n_LD - 2)``: the adjusted r^2 of LD-score regression).  `R` as in `dot`: unit diagonal, off-diagonal
+        entries ``dq_scale * stored``.  `set_active_blocks` does not filter the call."""
+        if weights is None:
+            dt = np.dtype(float_precision)
+            if dt not in _FLOAT_CODE:
+                raise ValueError(f"float_precision: expected float32 or float64, got {float_precision}")
+            a = None
+            y = np.empty(self.m, dtype=dt)
+            n_cols = 1
+        else:
+            A = np.asarray(weights)
+            if A.dtype not in _FLOAT_CODE:
+                raise ValueError(f"Buffer dtype mismatch for weights: expected float32 or float64, got {A.dtype}")
+            if A.ndim not in (1, 2) or A.shape[0] != self.m or (A.ndim == 2 and A.shape[1] < 1):
+                raise ValueError(f"weights: expected shape ({self.m},) or ({self.m}, G), got {A.shape}")
+            a = np.asfortranarray(A)
+            dt = a.dtype
+            y = np.empty(a.shape, dtype=dt, order="F")
+            n_cols = 1 if a.ndim == 1 else int(a.shape[1])
+        c = None
+        if correction is not None:
+            c = np.ascontiguousarray(correction, dtype=np.float64)
+            if c.shape != (self.m,):
+                raise ValueError(f"correction: expected shape ({self.m},), got {c.shape}")
+        if self.m == 0:
+            return y
+        L.check(L.lib.viprs_plan_ld_scores(self.handle, _FLOAT_CODE[dt], n_cols, _ptr(a), _ptr(c), _ptr(y), float(dq_scale)))
+        return y
+
+    def last_ld_score_ms(self):
+        """HIP-event time (ms) of the kernels of the last `ld_scores` on this plan."""
+        ms = ctypes.c_double(0.0)
+        L.check(L.lib.viprs_plan_last_ld_score_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     # -- ridge solve -----------------------------------------------------------------------------
     def solve_ridge(self, b, shift, dq_scale=1.0, rtol=None, maxiter=None, x0=None, check_every=4):
         """``(R + diag(shift)) x = b`` by one MINRES per LD block, all blocks in lock step (`viprs_plan_solve_ridge`; what

@@ -1,3 +1,4 @@
 """Statistics of the inputs computed on the device (the reference gets them from magenpy)."""
 from .spectrum import (UnpinnedLambdaMinError, annotate_spectrum, lambda_min_from_extremes,  # noqa: F401
                        ld_spectrum)
+from .ldsc import annotate_ld_scores, ld_scores, ld_scores_host, simple_ldsc  # noqa: F401
