@@ -488,6 +488,8 @@ int viprs_plan_last_ld_score_ms(viprs_plan* plan, double* ms);
  *   precision  vectors and the product in the state precision; every scalar and every dot product in double
  *   order      dot products: 16-byte chunks of the block dealt to 256 threads in turn, per-thread partial sums in ascending
  *              order, an xor butterfly over the 64 lanes, the wavefronts in order -- a function of the block's size alone;
+ *              a chunk is 16 bytes of the STATE precision: 16 / sizeof(T) consecutive elements (4 float32, 2 float64) in
+ *              every dot product of a solve, whatever the type of the values summed;
  *              no floating-point atomics.  A block's result does not depend on the other blocks of the plan, on
  *              `check_every` or on timing; two calls give identical bits
  *   outputs    block_iters / block_relres / block_status (each may be NULL), one entry per block: iterations done, the
@@ -524,7 +526,8 @@ int viprs_plan_last_solve_ms(viprs_plan* plan, double* total_ms, int* iterations
  *              brings appear at eigenvalues that have already converged and do no harm at the two ends, and the residual
  *              estimate below stays valid to O(eps ||A||) (Paige 1980)
  *   precision  vectors and the product in the state precision `float_dtype`; every scalar and every dot product in double
- *   order      dot products in the order of the ridge solve above: a function of the block's size alone; no floating-point
+ *   order      dot products in the order of the ridge solve above (the norm of the start vector u, whose values are doubles,
+ *              included: 16 / sizeof(T) elements to a chunk there too): a function of the block's size alone; no floating-point
  *              atomics.  A block's result does not depend on its place in the plan, on the other blocks or on timing; two
  *              calls give identical bits
  *   stopping   at k = 1, 2, 4, 8, ... and at max_iter the host takes the extreme Ritz pairs (theta, s) of the tridiagonal

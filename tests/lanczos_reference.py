@@ -21,9 +21,17 @@ both bounds are <= rtol * max(|theta_min|, |theta_max|), or when beta_{k+1} == 0
 reason to stop: in finite precision the Ritz values at k = size are not the eigenvalues.
 
 Vectors are in the state precision T, every vector operation is one rounded operation in T with its scalar coefficient
-rounded to T first; scalars and dot products are float64.  A v is fl(fl(dq_scale) S) + v with S the off-diagonal sum (here:
-float64, rounded to T once -- the device sums in T in the product's own order).  Here `np.linalg.eigh` is applied to T_k; the
-C library has its own implicit-QL routine (`viprs_tridiagonal_extremes`).
+rounded to T first; scalars and dot products are float64.  A v is fl(fl(dq_scale) S) + v with S the off-diagonal sum.
+
+What the header gives an ORDER or a routine for is a seam (`lanczos_block(..., off=, dot=, ritz=)`,
+`extremal_eigenvalues(..., off_product=, dot=, ritz=)`):
+    off(v)              S, the off-diagonal sum of a block, in T.  Default: float64 matrix product, rounded to T once
+    dot(a, b)           a float64 value (the norm of the start vector included).  Default: `np.dot` of the float64 copies
+    ritz(alpha, beta)   the extreme Ritz pairs of T_k.  Default: `np.linalg.eigh` (`ritz_extremes` below); the C library has
+                        its own implicit-QL routine (`viprs_tridiagonal_extremes`)
+With the defaults this is a model of the recurrence, not of the device's bits.  With the replays of tests/order_replay.py in
+the seams (the product's own order in T, the 256-thread order of the dot products, the library's QL routine) it IS the
+device's arithmetic, operation by operation: the GPU tests compare all six outputs with `==`.
 
 status: 0 converged, 1 stopped at maxiter (the current Ritz values and bounds are still returned).
 """
@@ -64,25 +72,30 @@ def ritz_extremes(alpha, beta):
     return theta[0], theta[-1], beta[k - 1] * abs(S[-1, 0]), beta[k - 1] * abs(S[-1, -1])
 
 
-def _dot(a, b):
+def _default_dot(a, b):
     return float(np.dot(a.astype(np.float64), b.astype(np.float64)))
 
 
-def lanczos_block(R_off, dq, rtol, maxiter, dtype):
-    """One block.  R_off: stored off-diagonal entries (float64, not dequantised); dq a T scalar.
+def lanczos_block(R_off, dq, rtol, maxiter, dtype, off=None, dot=None, ritz=None, n=None):
+    """One block.  R_off: stored off-diagonal entries (float64, not dequantised; unused with `off`, which needs the size
+    `n`); dq a T scalar.  `off`, `dot`, `ritz`: the seams of the module docstring.
     Returns (theta_min, theta_max, resid_min, resid_max, iterations, status)."""
     dtype = np.dtype(dtype)
     T = dtype.type
-    n = R_off.shape[0]
+    n = R_off.shape[0] if n is None else int(n)
+    if off is None:
+        off = lambda v: (R_off @ v.astype(np.float64)).astype(dtype)
+    _dot = _default_dot if dot is None else dot
+    ritz = ritz_extremes if ritz is None else ritz
     u = start_vector(n)
-    v = (u / np.sqrt(float(np.dot(u, u)))).astype(dtype)
+    v = (u / np.sqrt(_dot(u, u))).astype(dtype)
     v_prev = np.zeros(n, dtype=dtype)
     alpha, beta = [], []
     b = 0.0
     checks = set(check_points(maxiter))
     out = None
     for k in range(1, int(maxiter) + 1):
-        w = (dq * (R_off @ v.astype(np.float64)).astype(dtype)) + v
+        w = (dq * off(v)) + v
         w = w - T(b) * v_prev
         a = _dot(v, w)
         w = w - T(a) * v
@@ -90,7 +103,7 @@ def lanczos_block(R_off, dq, rtol, maxiter, dtype):
         alpha.append(a)
         beta.append(b)
         if b == 0.0 or k in checks:
-            lo, hi, r_lo, r_hi = out = ritz_extremes(alpha, beta)
+            lo, hi, r_lo, r_hi = out = ritz(alpha, beta)
             scale = max(abs(lo), abs(hi))
             if b == 0.0 or (r_lo <= rtol * scale and r_hi <= rtol * scale):
                 return lo, hi, r_lo, r_hi, k, SpectrumInfo.CONVERGED
@@ -98,8 +111,10 @@ def lanczos_block(R_off, dq, rtol, maxiter, dtype):
     return out + (int(maxiter), SpectrumInfo.MAXITER)
 
 
-def extremal_eigenvalues(lb, ip, data, low_memory, dq_scale=1.0, rtol=None, maxiter=None, float_precision="float32"):
-    """The host model over every block: a `SpectrumInfo` like `LDPlan.extremal_eigenvalues` returns."""
+def extremal_eigenvalues(lb, ip, data, low_memory, dq_scale=1.0, rtol=None, maxiter=None, float_precision="float32",
+                         off_product=None, dot=None, ritz=None):
+    """The host model over every block: a `SpectrumInfo` like `LDPlan.extremal_eigenvalues` returns.  `off_product(s, e)`
+    gives the `off` of block [s, e) (None: the float64 matrix product); `dot` and `ritz` are handed to every block."""
     lb, ip = np.asarray(lb), np.asarray(ip, dtype=np.int64)
     dtype = np.dtype(float_precision)
     assert dtype in (np.float32, np.float64)
@@ -109,8 +124,9 @@ def extremal_eigenvalues(lb, ip, data, low_memory, dq_scale=1.0, rtol=None, maxi
     data64 = np.asarray(data, dtype=np.float64)
     rows = []
     for s, e in blocks_of(lb, ip, low_memory):
-        R, _ = block_matrix(lb, ip, data64, low_memory, s, e)
-        rows.append(lanczos_block(R, dq, rtol, maxiter, dtype))
+        R = block_matrix(lb, ip, data64, low_memory, s, e)[0] if off_product is None else None
+        rows.append(lanczos_block(R, dq, rtol, maxiter, dtype, None if off_product is None else off_product(s, e), dot,
+                                  ritz, e - s))
     cols = list(zip(*rows)) if rows else [[]] * 6
     return SpectrumInfo(*cols)
 

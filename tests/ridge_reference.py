@@ -19,7 +19,14 @@ converged x0 comes back at once (scipy measures against ||b - A x0|| and would i
 
 Vectors are in the state precision T, every vector operation is one rounded operation in T with its scalar coefficient
 rounded to T first; scalars and dot products are float64.  A v is fl(fl(dq_scale) S) + v + fl(shift) v with S the
-off-diagonal sum (here: float64, rounded to T once -- the device sums in T in the product's own order).
+off-diagonal sum.
+
+The two sums the header gives an ORDER for are seams (`minres_block(..., off=, dot=)`, `solve(..., off_product=, dot=)`):
+    off(v)     S, the off-diagonal sum of a block, in T.  Default: float64 matrix product, rounded to T once -- a model of
+               the recurrences, not of the device's bits
+    dot(a, b)  a float64 value.  Default: `np.dot` of the float64 copies
+With the replays of tests/order_replay.py in both seams (the product's own order in T, the 256-thread order of the dot
+products) the model IS the device's arithmetic, operation by operation: the GPU tests compare it with `==`.
 
 status: 0 converged, 1 stopped at maxiter, 2 zero right-hand side (x = 0, no iteration).
 """
@@ -84,16 +91,20 @@ def condition_numbers(systems):
     return out
 
 
-def _dot(a, b):
+def _default_dot(a, b):
     return float(np.dot(a.astype(np.float64), b.astype(np.float64)))
 
 
-def minres_block(R_off, b, sh, dq, rtol, maxiter, x0=None):
-    """One block.  R_off: stored off-diagonal entries (float64, not dequantised); b, sh, x0 in T; dq a T scalar."""
+def minres_block(R_off, b, sh, dq, rtol, maxiter, x0=None, off=None, dot=None):
+    """One block.  R_off: stored off-diagonal entries (float64, not dequantised; unused with `off`); b, sh, x0 in T; dq a T
+    scalar.  `off`, `dot`: the seams of the module docstring."""
     T = b.dtype.type
+    if off is None:
+        off = lambda v: (R_off @ v.astype(np.float64)).astype(b.dtype)
+    _dot = _default_dot if dot is None else dot
 
     def matvec(v):
-        y = dq * (R_off @ v.astype(np.float64)).astype(b.dtype)
+        y = dq * off(v)
         y = y + v
         return y + sh * v
 
@@ -147,8 +158,9 @@ def minres_block(R_off, b, sh, dq, rtol, maxiter, x0=None):
     return x, itn, phibar / bnorm, status
 
 
-def solve(lb, ip, data, low_memory, b, shift, dq_scale=1.0, rtol=None, maxiter=None, x0=None):
-    """The host model over every block: `(x, RidgeInfo)` -- the signature of `LDPredInf(solve_fn=...)`."""
+def solve(lb, ip, data, low_memory, b, shift, dq_scale=1.0, rtol=None, maxiter=None, x0=None, off_product=None, dot=None):
+    """The host model over every block: `(x, RidgeInfo)` -- the signature of `LDPredInf(solve_fn=...)`.  `off_product(s, e)`
+    gives the `off` of block [s, e) (None: the float64 matrix product), `dot` is handed to every block."""
     lb, ip = np.asarray(lb), np.asarray(ip, dtype=np.int64)
     b = np.asarray(b)
     dtype = b.dtype
@@ -166,9 +178,10 @@ def solve(lb, ip, data, low_memory, b, shift, dq_scale=1.0, rtol=None, maxiter=N
     data64 = np.asarray(data, dtype=np.float64)
     with np.errstate(over="ignore", invalid="ignore"):
         for s, e in blocks:
-            R, _ = block_matrix(lb, ip, data64, low_memory, s, e)
+            R = block_matrix(lb, ip, data64, low_memory, s, e)[0] if off_product is None else None
             xb, it, rr, st = minres_block(R, b[s:e], sh[s:e], dq, float(rtol), int(maxiter),
-                                          None if x0 is None else np.asarray(x0)[s:e])
+                                          None if x0 is None else np.asarray(x0)[s:e],
+                                          None if off_product is None else off_product(s, e), dot)
             x[s:e] = xb
             iters.append(it)
             relres.append(rr)

@@ -1,7 +1,8 @@
 """The LD product `viprs_plan_dot` / `viprs_state_dot` (include/viprs_hip.h) against the host reference of
 tests/ld_dot_reference.py: exact cases compared with `==`, random cases against the rounding bound the header's order
-contract implies, independence / determinism, the state entry point, consistency with the sweep's own `q`, and the model
-layer (pseudo-validation against an external LD panel)."""
+contract implies, every bit against the host replay of the header's order (tests/order_replay.py), independence /
+determinism, the state entry point, consistency with the sweep's own `q`, and the model layer (pseudo-validation against an
+external LD panel)."""
 import functools
 import os
 
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import ld_dot_reference as R
+from tests import order_replay as OR
 from viprs_amd.utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -195,6 +197,121 @@ def test_rounding_bound(gpu, low_memory, T):
             print(f"rounding upper={low_memory} {np.dtype(T).name} diag={inc}: worst err/bound = "
                   f"{float(np.max(err / np.maximum(bound, np.finfo(np.float64).tiny))):.4f}")
             assert np.all(err <= bound)
+    finally:
+        plan.close()
+
+
+# ---- every bit against the host replay of THE ORDER ------------------------------------------------------------------------
+# the smallest sizes that cross every edge of the order: one 16-byte load, one pass of a wavefront at V = 4 / 8 / 16 (256 /
+# 512 / 1024 columns) and two, sizes that are no multiple of V or of the dense kernel's rows per wavefront; then one
+# jittered windowed component (gaps in the windows of the upper form)
+REPLAY_SIZES = (1, 2, 63, 65, 257, 513, 1025, 1537)
+REPLAY_LD = {"int8": np.int8, "int16": np.int16, "fp32": np.float32, "int32": np.int32, "fp64": np.float64}
+REPLAY_COLS = (1, 3, 33)
+
+
+def _unrepresentable(ld):
+    """Float64 LD whose values are NOT float32 values: every entry (i, j) of a block times 1 + 2^-26 t_ij, t symmetric in
+    (-1, 1) -- the conversion to a float32 state rounds."""
+    rng = np.random.default_rng(23)
+    data = ld.ld_data.astype(np.float64)
+    o = 0
+    for b in np.diff(ld.block_start):
+        b = int(b)
+        P = np.triu(rng.uniform(-1.0, 1.0, (b, b)), 1)
+        P = 1.0 + 2.0 ** -26 * (P + P.T)
+        if ld.low_memory:
+            for r in range(b - 1):
+                data[o:o + b - 1 - r] *= P[r, r + 1:]
+                o += b - 1 - r
+        else:
+            data[o:o + b * b] *= P.ravel()
+            o += b * b
+    return data
+
+
+@functools.lru_cache(maxsize=None)
+def replay_case(ld_name, low_memory):
+    """(left_bound, indptr, data, block starts): the dense blocks of REPLAY_SIZES with full-range "longrange" LD, then one
+    windowed component of 2500 SNPs with uniform entries.  Computed once, never modified."""
+    ld_dtype = np.dtype(REPLAY_LD[ld_name])
+    ld = syn.make_ld(REPLAY_SIZES, low_memory=low_memory, ld_dtype=np.float32 if ld_name == "fp64" else ld_dtype,
+                     kind="longrange", seed=5)
+    dense = _unrepresentable(ld) if ld_name == "fp64" else ld.ld_data
+    m0 = ld.m
+    lb_w, ip_w = _banded_windows(2500, 90, 140, low_memory, seed=14, jitter=60)
+    u = np.random.default_rng(24).uniform(-1.0, 1.0, int(ip_w[-1]))
+    band = np.rint(u * np.iinfo(ld_dtype).max).astype(ld_dtype) if np.issubdtype(ld_dtype, np.integer) else u.astype(ld_dtype)
+    lb = np.concatenate([ld.ld_left_bound, lb_w + m0]).astype(np.int32)
+    ip = np.concatenate([np.asarray(ld.ld_indptr, dtype=np.int64), ip_w[1:] + int(ld.ld_indptr[-1])])
+    data = np.concatenate([dense, band])
+    assert data.dtype == ld_dtype
+    if ld_name == "fp64":
+        assert np.mean(data.astype(np.float32).astype(np.float64) != data) > 0.9
+    starts = np.concatenate([ld.block_start, [m0 + 2500]]).astype(np.int64)
+    for a in (lb, ip, data, starts):
+        a.setflags(write=False)
+    return lb, ip, data, starts
+
+
+@functools.lru_cache(maxsize=None)
+def replay_inputs(T):
+    """Gaussian B, (m, 33) column-major in T (float64: full-precision values), shared by every case."""
+    m = sum(REPLAY_SIZES) + 2500
+    B = np.asfortranarray(np.random.default_rng(25).standard_normal((m, max(REPLAY_COLS))).astype(T))
+    B.setflags(write=False)
+    return B
+
+
+@functools.lru_cache(maxsize=None)
+def replayed_product(ld_name, low_memory, T):
+    """S of every column in the header's order: one replay per case (a column depends on nothing but itself)."""
+    lb, ip, data, _ = replay_case(ld_name, low_memory)
+    S = OR.replay_dot(lb, ip, data, low_memory, replay_inputs(T))
+    S.setflags(write=False)
+    return S
+
+
+def first_difference(got, want, starts):
+    """'' if the arrays are equal, else the count, the first differing row, its block and the two values."""
+    bad = np.asarray(got) != np.asarray(want)
+    if not bad.any():
+        return ""
+    at = tuple(int(i) for i in np.argwhere(bad)[0])
+    block = int(np.searchsorted(starts, at[0], side="right") - 1)
+    return (f"{int(bad.sum())} of {bad.size} entries differ, first at {at}: row {at[0] - int(starts[block])} of block "
+            f"{block} (size {int(starts[block + 1] - starts[block])}), device {got[at]!r} replay {want[at]!r}")
+
+
+@pytest.mark.parametrize("T", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("low_memory", [False, True], ids=["sym", "upper"])
+@pytest.mark.parametrize("ld_name", sorted(REPLAY_LD))
+def test_bits_are_the_headers_order(gpu, ld_name, low_memory, T):
+    """`got == finish(replay)` and nothing else: for finite inputs the header makes the product a fixed function of its
+    inputs -- entry e to accumulator e % V of lane (e / V) % 64, one FMA per entry in T, the tree over V, the butterfly over
+    the lanes, then two rounded operations.  Random full-range LD and Gaussian B: an unfused multiply-add, a truncating
+    conversion (int32 / fp64 LD in a float32 state), another lane assignment or tree changes most rows."""
+    from viprs_amd import _lib as L
+    from viprs_amd.plan import LDPlan
+    lb, ip, data, starts = replay_case(ld_name, low_memory)
+    B, S = replay_inputs(T), replayed_product(ld_name, low_memory, T)
+    plan = LDPlan(lb, ip, data, low_memory)
+
+    def check(storage):
+        for n in REPLAY_COLS:
+            Bn, Sn = (B[:, :n], S[:, :n]) if n > 1 else (B[:, 0], S[:, 0])
+            for dq in (1.0, 1.0 / 127.0):
+                for inc in (False, True):
+                    got = plan.dot(Bn, dq_scale=dq, include_diagonal=inc)
+                    diff = first_difference(got, R.finish(Sn, Bn, dq, inc, T), starts)
+                    assert not diff, (f"{ld_name} upper={low_memory} {np.dtype(T).name} {storage} n_cols={n} dq={dq} "
+                                      f"diag={inc}: {diff}")
+    try:
+        check("as created")
+        if low_memory:
+            _float64_sweep(plan)
+            assert plan.info(L.INFO_N_DENSE) == 0 or plan.info(L.INFO_UPPER_MIRRORED) == 0
+            check("zero lower triangle")
     finally:
         plan.close()
 

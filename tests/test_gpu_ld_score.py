@@ -1,6 +1,7 @@
 """The LD scores `viprs_plan_ld_scores` (include/viprs_hip.h) against the host reference of tests/ld_score_reference.py:
-exact cases compared with `==`, random cases against the rounding bound of the header's definition, independence /
-determinism, and the model layer (`LDPredInf(gdl)`, `h2_init="ldsc"`, `annotate_ld_scores`)."""
+exact cases compared with `==`, random cases against the rounding bound of the header's definition, every bit against the
+host replay of the header's order (tests/order_replay.py), independence / determinism, and the model layer
+(`LDPredInf(gdl)`, `h2_init="ldsc"`, `annotate_ld_scores`)."""
 import ctypes
 import functools
 
@@ -8,7 +9,8 @@ import numpy as np
 import pytest
 
 from tests import ld_score_reference as SR
-from tests.test_gpu_ld_dot import _banded_windows, _float64_sweep
+from tests import order_replay as OR
+from tests.test_gpu_ld_dot import REPLAY_LD, _banded_windows, _float64_sweep, first_difference, replay_case
 from viprs_amd.utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -155,6 +157,71 @@ def test_rounding_bound(gpu, kind, ld_name, low_memory, T):
                       f"{float(np.max(err / np.maximum(bound, np.finfo(np.float64).tiny))):.4f}")
                 assert np.all(err <= bound)
                 assert np.any(got != (1.0 if An is None else An.astype(np.float64)))
+    finally:
+        plan.close()
+
+
+# ---- every bit against the host replay of THE ORDER ------------------------------------------------------------------------
+REPLAY_COLS = (1, 3, 7)        # the kernels carry 4, 2 or 1 columns per pass over a row: 7 = 4 + 2 + 1, 3 = 2 + 1
+
+
+@functools.lru_cache(maxsize=None)
+def replay_weights(T):
+    """Gaussian weights, (m, 7) column-major in T, and the correction c_j (doubles), shared by every case."""
+    m = replay_case("int8", False)[0].shape[0]
+    rng = np.random.default_rng(26)
+    A = np.asfortranarray(rng.standard_normal((m, max(REPLAY_COLS))).astype(T))
+    corr = rng.uniform(0.0, 0.01, m)
+    A.setflags(write=False)
+    corr.setflags(write=False)
+    return A, corr
+
+
+@functools.lru_cache(maxsize=None)
+def replayed_sums(ld_name, low_memory, T):
+    """((S2, S0) for the Gaussian weights, (S2, S0) for unit weights) in the header's order: one replay per case."""
+    lb, ip, data, _ = replay_case(ld_name, low_memory)
+    out = (OR.replay_scores(lb, ip, data, low_memory, replay_weights(T)[0], T),
+           OR.replay_scores(lb, ip, data, low_memory, None, T))
+    for pair in out:
+        for a in pair:
+            a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("T", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("low_memory", [False, True], ids=["sym", "upper"])
+@pytest.mark.parametrize("ld_name", sorted(REPLAY_LD))
+def test_bits_are_the_headers_order(gpu, ld_name, low_memory, T):
+    """`got == finish(replay)` and nothing else, on the matrix of the product's test: p = fl(x x), S2 by fma(p, a, acc) and
+    S0 by plain additions into the slots of THE ORDER, then the header's epilogue operation by operation.  Gaussian and unit
+    weights, with and without the correction, both storages of the upper form."""
+    from viprs_amd import _lib as L
+    from viprs_amd.plan import LDPlan
+    lb, ip, data, starts = replay_case(ld_name, low_memory)
+    dq = 1.0 if np.issubdtype(data.dtype, np.floating) else 1.0 / np.iinfo(data.dtype).max
+    (A, corr), ((S2, S0), (U2, U0)) = replay_weights(T), replayed_sums(ld_name, low_memory, T)
+    plan = LDPlan(lb, ip, data, low_memory)
+
+    def check(storage):
+        for n in REPLAY_COLS + (None,):
+            if n is None:
+                An, s2, s0 = None, U2, U0
+            elif n == 1:
+                An, s2, s0 = A[:, 0], S2[:, 0], S0[:, 0]
+            else:
+                An, s2, s0 = A[:, :n], S2[:, :n], S0[:, :n]
+            for c in (None, corr):
+                got = plan.ld_scores(An, c, dq_scale=dq, float_precision=np.dtype(T).name)
+                diff = first_difference(got, SR.finish(s2, s0, An, c, dq, T), starts)
+                assert not diff, (f"{ld_name} upper={low_memory} {np.dtype(T).name} {storage} n_cols={n} "
+                                  f"corr={c is not None}: {diff}")
+    try:
+        check("as created")
+        if low_memory:
+            _float64_sweep(plan)
+            assert plan.info(L.INFO_N_DENSE) == 0 or plan.info(L.INFO_UPPER_MIRRORED) == 0
+            check("zero lower triangle")
     finally:
         plan.close()
 

@@ -1,7 +1,8 @@
 """The ridge solve `viprs_plan_solve_ridge` (include/viprs_hip.h) on the device against the host model of
 tests/ridge_reference.py and a dense float64 solve: accuracy through the TRUE residual, indefinite systems, per-block
-stopping, zero right-hand sides, windowed LD, determinism / independence, warm starts, the model layer (`LDPredInf`) and
-solves between sweeps of the same plan.
+stopping, zero right-hand sides, windowed LD, every bit against the host model driven by the replays of the header's
+orders (tests/order_replay.py), determinism / independence, warm starts, the model layer (`LDPredInf`) and solves between
+sweeps of the same plan.
 
 The bounds: a block is accepted when its true residual ||b - A x|| / ||b||, evaluated in float64 from the dense block, is at
 most 2 rtol -- the solver stops on its own estimate <= rtol, the host model's estimate equals its true residual to within
@@ -14,7 +15,9 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+from tests import order_replay as OR
 from tests import ridge_reference as RR
+from tests.test_gpu_ld_dot import REPLAY_SIZES
 from viprs_amd.utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -304,3 +307,93 @@ def test_solve_between_sweeps_leaves_the_sweeps_alone(gpu, T):
             plan.close()
     for k in out[0]:
         assert np.array_equal(out[0][k], out[1][k]), k
+
+
+# ---- every bit against the replayed host model ----------------------------------------------------------------------------
+# REPLAY_SIZES (test_gpu_ld_dot): one 16-byte load, one wavefront pass of the product, one and two passes of the 256-thread
+# dot product in both precisions (1024 / 512 elements), sizes that are no multiple of the chunk
+REPLAY_CASES = ("ar1-fp32-sym", "longrange-int8-upper", "banded-sym", "banded-upper")
+# "to convergence": every block of every case below stops with status 0 well below this (asserted on the replayed model)
+REPLAY_MAXITER = 120
+
+
+@functools.lru_cache(maxsize=None)
+def replay_system(case):
+    """(left_bound, indptr, data, low_memory, dq_scale, b as float64, block starts) of a replay case."""
+    if case.startswith("banded"):
+        lb, ip, data, b, _ = _banded(case.endswith("upper"))
+        return lb, ip, data, case.endswith("upper"), 1.0, b, np.array([0, 2500])
+    ld, b = _ld(case, REPLAY_SIZES)
+    return ld.ld_left_bound, ld.ld_indptr, ld.ld_data, ld.low_memory, ld.dq_scale, b, np.asarray(ld.block_start)
+
+
+def replay_shift(kind, starts):
+    """0.5 (the single windowed block: 2.0 -- the truncated AR(1) band has condition number 110 at 0.5 and needs more than 100
+    iterations in float64), or a per-SNP vector whose sign alternates from block to block, the first one negative: +[0.4,
+    0.6] and -[8, 12].  A negative shift of the positive one's size leaves a block indefinite AND nearly singular (the
+    eigenvalues of an LD block are dense around 0.5: hundreds of iterations, the large blocks more than 600).  At -[8, 12]
+    every block converges within 40 iterations: the AR(1) blocks are negative definite there, the 257- and 1025-SNP
+    long-range blocks indefinite (their two factor eigenvalues stay positive).  The single windowed block takes the signs by
+    halves, +-[80, 120] (1250 negative and 1250 positive eigenvalues): its spectrum is dense up to 39, so the negative half
+    has to clear it."""
+    if kind == "scalar":
+        return 0.5 if len(starts) > 2 else 2.0
+    m = int(starts[-1])
+    mag = np.random.default_rng(33).uniform(0.4, 0.6, m)
+    edges = starts if len(starts) > 2 else np.array([0, m // 2, m])
+    sign = np.concatenate([np.full(int(e - s), -1.0 if k % 2 == 0 else 1.0)
+                           for k, (s, e) in enumerate(zip(edges[:-1], edges[1:]))])
+    if len(starts) == 2:
+        return 200.0 * sign * mag
+    return np.where(sign < 0, 20.0, 1.0) * sign * mag
+
+
+def _same_solve(name, got, want, starts):
+    (x, info), (xr, ir) = got, want
+    for field in ("iterations", "status", "relres"):
+        a, b = getattr(info, field), getattr(ir, field)
+        assert np.array_equal(a, b), (f"{name}: {field} of blocks {np.nonzero(a != b)[0].tolist()}: device {a.tolist()} "
+                                      f"replay {b.tolist()}")
+    bad = x != xr
+    if bad.any():
+        at = int(np.argwhere(bad)[0][0])
+        block = int(np.searchsorted(starts, at, side="right") - 1)
+        raise AssertionError(f"{name}: x differs in {int(bad.sum())} entries, first at SNP {at} (block {block}, size "
+                             f"{int(starts[block + 1] - starts[block])}): device {x[at]!r} replay {xr[at]!r}")
+
+
+@pytest.mark.parametrize("T", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("shift_kind", ["scalar", "vector"])
+@pytest.mark.parametrize("case", REPLAY_CASES)
+def test_bits_are_the_replayed_model(gpu, case, shift_kind, T):
+    """`x`, `iterations`, `relres` and `status` `==` the host model with the product in the header's order and the dot
+    products in the 256-thread order: every operation of the solver is then the device's.  The ladder of `maxiter` compares
+    the state after each of the first iterations (a failure points at the iteration where the two part), then the run to
+    convergence (status 0 in every block, asserted) under both `check_every`, then a warm start from a perturbed solution
+    (a few iterations remain)."""
+    from viprs_amd.plan import LDPlan
+    lb, ip, data, low_memory, dq, b64, starts = replay_system(case)
+    b = b64.astype(T)
+    shift = replay_shift(shift_kind, starts)
+    rtol = RTOL[T]
+    replay = lambda **kw: OR.replayed_solve(lb, ip, data, low_memory, b, shift, dq, rtol, **kw)
+    name = f"{case} {shift_kind} {np.dtype(T).name}"
+    plan = LDPlan(lb, ip, data, low_memory)
+    try:
+        device = lambda **kw: plan.solve_ridge(b, shift, dq_scale=dq, rtol=rtol, **kw)
+        for k in (1, 2, 3, 5, 8):
+            _same_solve(f"{name} maxiter={k}", device(maxiter=k, check_every=1), replay(maxiter=k), starts)
+        want = replay(maxiter=REPLAY_MAXITER)
+        print(name, "iterations", want[1].iterations.tolist(), "status", want[1].status.tolist())
+        assert np.all(want[1].status == 0) and 8 < want[1].iterations.max() < REPLAY_MAXITER
+        for ce in (1, 7):
+            _same_solve(f"{name} check_every={ce}", device(maxiter=REPLAY_MAXITER, check_every=ce), want, starts)
+        x0 = (want[0] * (1 + T(1e-3) * np.random.default_rng(34).standard_normal(b.shape[0]).astype(T))).astype(T)
+        warm = replay(maxiter=REPLAY_MAXITER, x0=x0)
+        print(name, "warm start iterations", warm[1].iterations.tolist())
+        assert np.all(warm[1].status == 0) and warm[1].iterations.max() > 0
+        assert np.all(warm[1].iterations <= want[1].iterations)
+        for ce in (1, 7):
+            _same_solve(f"{name} x0 check_every={ce}", device(maxiter=REPLAY_MAXITER, check_every=ce, x0=x0), warm, starts)
+    finally:
+        plan.close()

@@ -1,7 +1,8 @@
 """The extremal eigenvalues `viprs_plan_extremal_eigenvalues` (include/viprs_hip.h) on the device against
 `np.linalg.eigvalsh` of the dense blocks and the host model of tests/lanczos_reference.py: accuracy at both ends, windowed
-LD with a negative eigenvalue, the status at maxiter, determinism / independence, calls between sweeps of the same plan and
-the model layer (`annotate_spectrum`, `lambda_min='compute'`).
+LD with a negative eigenvalue, the status at maxiter, every bit against the host model driven by the replays of the header's
+orders (tests/order_replay.py), determinism / independence, calls between sweeps of the same plan and the model layer
+(`annotate_spectrum`, `lambda_min='compute'`).
 
 The bounds: a block stops when its two residual bounds are <= rtol * scale, and a Ritz value lies within its residual bound
 of an eigenvalue, so |theta - lambda| <= rtol * max(|lambda_min|, |lambda_max|) at both ends once the Ritz values have
@@ -14,7 +15,9 @@ import numpy as np
 import pytest
 
 from tests import lanczos_reference as LR
+from tests import order_replay as OR
 from tests import ridge_reference as RR
+from tests.test_gpu_ld_dot import REPLAY_SIZES
 from viprs_amd.utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -260,3 +263,47 @@ def test_model_layer(gpu):
     # 'compute' needs the device
     with pytest.raises(RuntimeError, match="HIP device"):
         VIPRS(make(), lambda_min="compute", e_step_fn=lambda *a: None)
+
+
+# ---- every bit against the replayed host model ----------------------------------------------------------------------------
+REPLAY_CASES = ("ar1-fp32-sym", "longrange-int8-upper", "banded-sym", "banded-upper")
+# the run to convergence: `==` needs no accurate eigenvalue, so the tolerance is one that every block -- the windowed band
+# included -- meets at one of the check points k = 16, 32, 64, 128 (status 0 in every block, asserted on the replayed model);
+# maxiter lies above the last of them and is no power of two
+REPLAY_RTOL = 1e-3
+REPLAY_MAXITER = 160
+FIELDS = ("iterations", "status", "lambda_min", "lambda_max", "resid_min", "resid_max")
+
+
+@functools.lru_cache(maxsize=None)
+def replay_matrix(case):
+    if case.startswith("banded"):
+        lb, ip, data, _ = _banded(case.endswith("upper"))
+        return lb, ip, data, case.endswith("upper"), 1.0
+    ld = _ld(case, REPLAY_SIZES)
+    return ld.ld_left_bound, ld.ld_indptr, ld.ld_data, ld.low_memory, ld.dq_scale
+
+
+@pytest.mark.parametrize("T", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("case", REPLAY_CASES)
+def test_bits_are_the_replayed_model(gpu, case, T):
+    """All six outputs `==` the host model with the product in the header's order, the dot products (the norm of the start
+    vector included) in the 256-thread order and the library's own QL routine for the Ritz pairs.  The ladder of `maxiter`
+    compares the coefficients' consequences after the first steps (3 and 5 fall between the check points), then the run
+    to convergence: every block stops with status 0 at a check point between the ladder and `maxiter`."""
+    from viprs_amd.plan import LDPlan
+    lb, ip, data, low_memory, dq = replay_matrix(case)
+    name = f"{case} {np.dtype(T).name}"
+    plan = LDPlan(lb, ip, data, low_memory)
+    try:
+        for k in (1, 2, 3, 5, 16, REPLAY_MAXITER):
+            want = OR.replayed_spectrum(lb, ip, data, low_memory, dq, REPLAY_RTOL, k, T)
+            got = plan.extremal_eigenvalues(dq_scale=dq, rtol=REPLAY_RTOL, maxiter=k, float_precision=T)
+            for field in FIELDS:
+                a, b = getattr(got, field), getattr(want, field)
+                assert np.array_equal(a, b), (f"{name} maxiter={k}: {field} of blocks {np.nonzero(a != b)[0].tolist()}: "
+                                              f"device {a.tolist()} replay {b.tolist()}")
+        print(name, "iterations", want.iterations.tolist(), "status", want.status.tolist())
+        assert np.all(want.status == 0) and 16 < want.iterations.max() < REPLAY_MAXITER
+    finally:
+        plan.close()
