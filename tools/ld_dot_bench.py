@@ -4,9 +4,9 @@
 
     python tools/ld_dot_bench.py [--config cfg3] [--calls 20] [--sweeps 5]
 
-For {fp32, int8} LD x {upper, symmetric} x n_cols in {1, 32} x {float32, float64}: warm-up, then the mean of
-`last_dot_ms` over `--calls` products through `DeviceState.dot` (B is the resident eta: no upload inside the bracket) and
-the mean sweep-kernel time (`plan.timing_history(0)`) of the same state in the same process.  bytes = stored LD bytes of
+For {fp32, int8} LD x {upper, symmetric} x n_cols in {1, 32} x {float32, float64}: warm-up, then the mean (and the
+median, minimum and maximum) of `last_dot_ms` over `--calls` products through `DeviceState.dot` (B is the resident eta: no
+upload inside the bracket) and the mean sweep-kernel time (`plan.timing_history(0)`) of the same state in the same process.  bytes = stored LD bytes of
 the device layout + 2 m n_cols sizeof(T); `frac_peak` is against 8 TB/s, `vs_model` = time / (bytes / 6.3 TB/s).
 Upper form: a float64 state's sweeps leave the dense blocks with a zero lower triangle, which the product reads in place
 (`storage: "zero-lower"`); fp32 states leave them mirrored."""
@@ -81,7 +81,9 @@ def main():
                     nbytes = ld_bytes + 2 * m * n_cols * np.dtype(T).itemsize
                     rows.append({"ld": ld_name, "form": "upper" if low_memory else "symmetric", "state": T, "n_cols": n_cols,
                                  "storage": "zero-lower" if (low_memory and T == "float64") else ("mirrored" if low_memory else "symmetric"),
-                                 "dot_ms": round(dot_ms, 4), "dot_ms_min": round(float(np.min(t)), 4), "sweep_ms": round(sweep_ms, 4),
+                                 "dot_ms": round(dot_ms, 4), "dot_ms_min": round(float(np.min(t)), 4),
+                                 "dot_ms_median": round(float(np.median(t)), 4), "dot_ms_max": round(float(np.max(t)), 4),
+                                 "sweep_ms": round(sweep_ms, 4),
                                  "dot_over_sweep": round(dot_ms / sweep_ms, 3), "bytes": int(nbytes),
                                  "frac_peak": round(nbytes / (dot_ms * 1e-3) / PEAK, 3),
                                  "vs_model": round(dot_ms * 1e-3 / (nbytes / COPY), 2)})

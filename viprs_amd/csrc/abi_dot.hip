@@ -6,7 +6,7 @@ using namespace viprs;
 
 // Tables of the product: every block of the plan (the active-block filter of the sweeps does not apply), one work item per
 // row, in the order of the plan's full block lists (the dense blocks as the schedule sorted them, then the windowed ones).
-int viprs::build_dot_tables(viprs_plan* P) {
+static int build_dot_tables(viprs_plan* P) {
     if (P->dot_built) return VIPRS_OK;
     std::vector<BlockDesc> blocks(P->dense_all_h);
     blocks.insert(blocks.end(), P->ragged_all_h.begin(), P->ragged_all_h.end());
@@ -48,24 +48,26 @@ int viprs::build_dot_tables(viprs_plan* P) {
         HIP_TRY(P->d_dot_first.alloc(m));
         HIP_TRY(hipMemcpy(P->d_dot_first.p, first.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
     }
-    for (auto& e : P->ev_dot)
-        if (!e) HIP_TRY(hipEventCreate(&e));
     P->dot_built = true;
     return VIPRS_OK;
 }
 
-// the kernels of one product on the plan's stream, between the product's own two events (internal.h: the ridge solve calls it too)
-int viprs::enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal) {
+int viprs::prepare_ld_rows(viprs_plan* P) {
     int rc = build_dot_tables(P);
     if (rc != VIPRS_OK) return rc;
     // Upper form: a plan nobody has swept yet holds the zero lower triangle only because the repack left it so -- mirror it
     // once, as the first fp32 sweep would.  A plan whose last sweep asked for the zero lower triangle (float64 state) keeps
     // it: the product reads that storage in place instead of converting the whole LD back and forth between EM rounds.
-    if (P->low_memory && !P->mirror && !P->unmirrored_wanted) {
-        rc = ensure_upper_storage(P, true);
-        if (rc != VIPRS_OK) return rc;
-    }
-    HIP_TRY(hipEventRecord(P->ev_dot[0], P->stream));
+    if (P->low_memory && !P->mirror && !P->unmirrored_wanted) return ensure_upper_storage(P, true);
+    return VIPRS_OK;
+}
+
+// the kernels of one product on the plan's stream, between the product's own two events (internal.h: the solvers call it too)
+int viprs::enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal) {
+    int rc = prepare_ld_rows(P);
+    if (rc != VIPRS_OK) return rc;
+    rc = P->time_dot.start(P->stream);
+    if (rc != VIPRS_OK) return rc;
     switch (P->ld_dtype) {
         case VIPRS_LD_I8: rc = launch_ld_dot<int8_t>(P, float_dtype, n_cols, dB, dY, dq_scale, include_diagonal); break;
         case VIPRS_LD_I16: rc = launch_ld_dot<int16_t>(P, float_dtype, n_cols, dB, dY, dq_scale, include_diagonal); break;
@@ -76,9 +78,7 @@ int viprs::enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* d
         default: return fail(VIPRS_EINVAL, "bad LD dtype code");
     }
     if (rc != VIPRS_OK) return rc;
-    HIP_TRY(hipEventRecord(P->ev_dot[1], P->stream));
-    P->dot_timed = true;
-    return VIPRS_OK;
+    return P->time_dot.stop(P->stream);
 }
 
 extern "C" {
@@ -125,13 +125,7 @@ int viprs_state_dot(viprs_state* S, int field, double dq_scale, int include_diag
 
 int viprs_plan_last_dot_ms(viprs_plan* P, double* ms) {
     if (!P || !ms) return fail(VIPRS_EINVAL, "null argument");
-    if (!P->dot_timed) return fail(VIPRS_EINVAL, "no timed product yet");
-    HIP_TRY(hipSetDevice(P->device));
-    HIP_TRY(hipEventSynchronize(P->ev_dot[1]));
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, P->ev_dot[0], P->ev_dot[1]));
-    *ms = (double)t;
-    return VIPRS_OK;
+    return P->time_dot.elapsed(P->device, ms, "no timed product yet");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // C ABI, LD scores (include/viprs_hip.h): l_j = sum_k a_k r_jk^2 over every block of a plan -- what the reference gets from
-// magenpy's `compute_ld_scores` and feeds to `simple_ldsc`.  Kernels: ld_score.h; tables: those of the product (abi_dot.hip).
+// magenpy's `compute_ld_scores` and feeds to `simple_ldsc`.  Kernels: ld_score.h on ld_rows.h; tables: those of the product (abi_dot.hip).
 #include "internal.h"
 
 using namespace viprs;
@@ -20,21 +20,14 @@ int viprs_plan_ld_scores(viprs_plan* P, int float_dtype, int n_cols, const void*
     if (a_host && P->d_score_a.n < bytes) HIP_TRY(P->d_score_a.alloc(bytes));
     if (P->d_score_y.n < bytes) HIP_TRY(P->d_score_y.alloc(bytes));
     if (corr_host && P->d_score_corr.n < m) HIP_TRY(P->d_score_corr.alloc(m));
-    int rc = build_dot_tables(P);
+    int rc = prepare_ld_rows(P);
     if (rc != VIPRS_OK) return rc;
-    for (auto& e : P->ev_score)
-        if (!e.e) HIP_TRY(hipEventCreate(&e.e));
-    // upper form: a plan nobody has swept yet is mirrored once, as the product does; the zero-lower-triangle storage of the
-    // float64 sweeps is read in place
-    if (P->low_memory && !P->mirror && !P->unmirrored_wanted) {
-        rc = ensure_upper_storage(P, true);
-        if (rc != VIPRS_OK) return rc;
-    }
     if (a_host) HIP_TRY(hipMemcpyAsync(P->d_score_a.p, a_host, bytes, hipMemcpyHostToDevice, P->stream));
     if (corr_host) HIP_TRY(hipMemcpyAsync(P->d_score_corr.p, corr_host, m * sizeof(double), hipMemcpyHostToDevice, P->stream));
     const void* dA = a_host ? P->d_score_a.p : nullptr;
     const double* dC = corr_host ? P->d_score_corr.p : nullptr;
-    HIP_TRY(hipEventRecord(P->ev_score[0].e, P->stream));
+    rc = P->time_score.start(P->stream);
+    if (rc != VIPRS_OK) return rc;
     switch (P->ld_dtype) {
         case VIPRS_LD_I8: rc = launch_ld_score<int8_t>(P, float_dtype, n_cols, dA, dC, P->d_score_y.p, dq_scale); break;
         case VIPRS_LD_I16: rc = launch_ld_score<int16_t>(P, float_dtype, n_cols, dA, dC, P->d_score_y.p, dq_scale); break;
@@ -45,8 +38,8 @@ int viprs_plan_ld_scores(viprs_plan* P, int float_dtype, int n_cols, const void*
         default: return fail(VIPRS_EINVAL, "bad LD dtype code");
     }
     if (rc != VIPRS_OK) return rc;
-    HIP_TRY(hipEventRecord(P->ev_score[1].e, P->stream));
-    P->score_timed = true;
+    rc = P->time_score.stop(P->stream);
+    if (rc != VIPRS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(P->stream));
     rc = check_device_error(P);
     if (rc != VIPRS_OK) return rc;
@@ -56,13 +49,7 @@ int viprs_plan_ld_scores(viprs_plan* P, int float_dtype, int n_cols, const void*
 
 int viprs_plan_last_ld_score_ms(viprs_plan* P, double* ms) {
     if (!P || !ms) return fail(VIPRS_EINVAL, "null argument");
-    if (!P->score_timed) return fail(VIPRS_EINVAL, "no timed LD-score call yet");
-    HIP_TRY(hipSetDevice(P->device));
-    HIP_TRY(hipEventSynchronize(P->ev_score[1].e));
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, P->ev_score[0].e, P->ev_score[1].e));
-    *ms = (double)t;
-    return VIPRS_OK;
+    return P->time_score.elapsed(P->device, ms, "no timed LD-score call yet");
 }
 
 }  // extern "C"

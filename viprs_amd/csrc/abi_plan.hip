@@ -132,7 +132,6 @@ viprs_plan::~viprs_plan() {
     viprs::team_launch_forget(this);           // (a later plan may get this address or this stream handle)
     delete scratch;
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_dot) if (e) (void)hipEventDestroy(e);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
     if (side_stream) (void)hipStreamDestroy(side_stream);

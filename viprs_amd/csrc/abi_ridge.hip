@@ -6,24 +6,30 @@
 
 using namespace viprs;
 
+int viprs::ensure_solver_blocks(viprs_plan* P) {
+    const size_t nb = P->blocks.size();
+    if (P->d_solver_blocks.p || nb == 0) return VIPRS_OK;
+    std::vector<RidgeBlock> blocks(nb);
+    for (size_t k = 0; k < nb; ++k) {
+        blocks[k].start = P->blocks[k].start;
+        blocks[k].size = (int32_t)(P->blocks[k].end - P->blocks[k].start);
+        blocks[k].pad_ = 0;
+    }
+    HIP_TRY(P->d_solver_blocks.alloc(nb));
+    HIP_TRY(hipMemcpy(P->d_solver_blocks.p, blocks.data(), nb * sizeof(RidgeBlock), hipMemcpyHostToDevice));
+    return VIPRS_OK;
+}
+
 namespace {
 
 int build_ridge_workspace(viprs_plan* P, size_t elem) {
     RidgeWork& W = P->ridge;
     const size_t nb = P->blocks.size();
+    int rc = ensure_solver_blocks(P);
+    if (rc != VIPRS_OK) return rc;
     if (!W.built) {
-        std::vector<RidgeBlock> blocks(nb);
-        for (size_t k = 0; k < nb; ++k) {
-            blocks[k].start = P->blocks[k].start;
-            blocks[k].size = (int32_t)(P->blocks[k].end - P->blocks[k].start);
-            blocks[k].pad_ = 0;
-        }
-        HIP_TRY(W.d_blocks.alloc(nb * sizeof(RidgeBlock)));
-        HIP_TRY(hipMemcpy(W.d_blocks.p, blocks.data(), nb * sizeof(RidgeBlock), hipMemcpyHostToDevice));
         HIP_TRY(W.d_rec.alloc(nb * sizeof(RidgeRec)));
         HIP_TRY(W.d_live.alloc(1));
-        for (auto& e : W.ev)
-            if (!e.e) HIP_TRY(hipEventCreate(&e.e));
         W.built = true;
     }
     const size_t bytes = (size_t)P->m * elem;
@@ -60,7 +66,7 @@ int solve_typed(viprs_plan* P, int float_dtype, const void* b_host, const double
     HIP_TRY(hipStreamSynchronize(P->stream));       // (the staging vector above goes out of use here)
 
     RidgeArgs<T> A;
-    A.blocks = reinterpret_cast<const RidgeBlock*>(W.d_blocks.p);
+    A.blocks = P->d_solver_blocks.p;
     A.rec = reinterpret_cast<RidgeRec*>(W.d_rec.p);
     A.live = W.d_live.p;
     A.Y = Y;
@@ -72,8 +78,8 @@ int solve_typed(viprs_plan* P, int float_dtype, const void* b_host, const double
     A.has_x0 = x0_host ? 1 : 0;
     A.itn = 0;
 
-    HIP_TRY(hipEventRecord(W.ev[0].e, P->stream));
-    int rc = VIPRS_OK;
+    int rc = W.time.start(P->stream);
+    if (rc != VIPRS_OK) return rc;
     if (x0_host) {
         rc = enqueue_dot(P, float_dtype, 1, x, Y, dq_scale, 1);
         if (rc != VIPRS_OK) return rc;
@@ -102,8 +108,8 @@ int solve_typed(viprs_plan* P, int float_dtype, const void* b_host, const double
             if (live == 0) break;
         }
     }
-    HIP_TRY(hipEventRecord(W.ev[1].e, P->stream));
-    W.timed = true;
+    rc = W.time.stop(P->stream);
+    if (rc != VIPRS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(P->stream));
     return check_device_error(P);
 }
@@ -145,14 +151,9 @@ int viprs_plan_solve_ridge(viprs_plan* P, int float_dtype, const void* b_host, c
 
 int viprs_plan_last_solve_ms(viprs_plan* P, double* total_ms, int* iterations) {
     if (!P || !total_ms) return fail(VIPRS_EINVAL, "null argument");
-    if (!P->ridge.timed) return fail(VIPRS_EINVAL, "no timed solve yet");
-    HIP_TRY(hipSetDevice(P->device));
-    HIP_TRY(hipEventSynchronize(P->ridge.ev[1].e));
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, P->ridge.ev[0].e, P->ridge.ev[1].e));
-    *total_ms = (double)t;
-    if (iterations) *iterations = P->ridge.iterations;
-    return VIPRS_OK;
+    const int rc = P->ridge.time.elapsed(P->device, total_ms, "no timed solve yet");
+    if (rc == VIPRS_OK && iterations) *iterations = P->ridge.iterations;
+    return rc;
 }
 
 }  // extern "C"

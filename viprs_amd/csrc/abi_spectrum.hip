@@ -81,21 +81,13 @@ void tridiagonal_extremes(int n, const double* a, const double* b, double* out) 
 int build_spectrum_workspace(viprs_plan* P, size_t elem, int max_iter) {
     SpectrumWork& W = P->spectrum;
     const size_t nb = P->blocks.size();
+    int rc = ensure_solver_blocks(P);
+    if (rc != VIPRS_OK) return rc;
     if (!W.built) {
-        std::vector<RidgeBlock> blocks(nb);
-        for (size_t k = 0; k < nb; ++k) {
-            blocks[k].start = P->blocks[k].start;
-            blocks[k].size = (int32_t)(P->blocks[k].end - P->blocks[k].start);
-            blocks[k].pad_ = 0;
-        }
-        HIP_TRY(W.d_blocks.alloc(nb * sizeof(RidgeBlock)));
-        HIP_TRY(hipMemcpy(W.d_blocks.p, blocks.data(), nb * sizeof(RidgeBlock), hipMemcpyHostToDevice));
         HIP_TRY(W.d_beta.alloc(nb));
         HIP_TRY(W.d_status.alloc(nb));
         HIP_TRY(W.d_iters.alloc(nb));
         HIP_TRY(W.d_live.alloc(1));
-        for (auto& e : W.ev)
-            if (!e.e) HIP_TRY(hipEventCreate(&e.e));
         W.built = true;
     }
     const size_t bytes = (size_t)P->m * elem;
@@ -146,7 +138,7 @@ int spectrum_typed(viprs_plan* P, int float_dtype, double dq_scale, double rtol,
     T* Y = reinterpret_cast<T*>(W.d_vec[2].p);
 
     LanczosArgs<T> A;
-    A.blocks = reinterpret_cast<const RidgeBlock*>(W.d_blocks.p);
+    A.blocks = P->d_solver_blocks.p;
     A.beta = W.d_beta.p;
     A.status = W.d_status.p;
     A.iters = W.d_iters.p;
@@ -162,7 +154,8 @@ int spectrum_typed(viprs_plan* P, int float_dtype, double dq_scale, double rtol,
     int32_t live = (int32_t)nb;
     HIP_TRY(hipMemcpyAsync(W.d_live.p, &live, sizeof(live), hipMemcpyHostToDevice, P->stream));
     HIP_TRY(hipStreamSynchronize(P->stream));           // (`live` above is a local)
-    HIP_TRY(hipEventRecord(W.ev[0].e, P->stream));
+    int rc = W.time.start(P->stream);
+    if (rc != VIPRS_OK) return rc;
     lanczos_init_kernel<T><<<(unsigned)nb, kRidgeThreads, 0, P->stream>>>(A);
     HIP_TRY(hipGetLastError());
 
@@ -177,7 +170,7 @@ int spectrum_typed(viprs_plan* P, int float_dtype, double dq_scale, double rtol,
     int k_prev = 0, next_check = 1;
     size_t n_running = nb;
     for (int k = 1; k <= max_iter && n_running > 0; ++k) {
-        int rc = enqueue_dot(P, float_dtype, 1, v, Y, dq_scale, 1);
+        rc = enqueue_dot(P, float_dtype, 1, v, Y, dq_scale, 1);
         if (rc != VIPRS_OK) return rc;
         A.k = k;
         lanczos_step_kernel<T><<<(unsigned)nb, kRidgeThreads, 0, P->stream>>>(A);
@@ -237,8 +230,8 @@ int spectrum_typed(viprs_plan* P, int float_dtype, double dq_scale, double rtol,
         k_prev = k;
         next_check *= 2;
     }
-    HIP_TRY(hipEventRecord(W.ev[1].e, P->stream));
-    W.timed = true;
+    rc = W.time.stop(P->stream);
+    if (rc != VIPRS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(P->stream));
     return check_device_error(P);
 }
@@ -276,12 +269,8 @@ int viprs_plan_extremal_eigenvalues(viprs_plan* P, int float_dtype, double dq_sc
 
 int viprs_plan_last_spectrum_ms(viprs_plan* P, double* total_ms, int* iterations, double* host_ms) {
     if (!P || !total_ms) return fail(VIPRS_EINVAL, "null argument");
-    if (!P->spectrum.timed) return fail(VIPRS_EINVAL, "no timed spectrum yet");
-    HIP_TRY(hipSetDevice(P->device));
-    HIP_TRY(hipEventSynchronize(P->spectrum.ev[1].e));
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, P->spectrum.ev[0].e, P->spectrum.ev[1].e));
-    *total_ms = (double)t;
+    const int rc = P->spectrum.time.elapsed(P->device, total_ms, "no timed spectrum yet");
+    if (rc != VIPRS_OK) return rc;
     if (iterations) *iterations = P->spectrum.iterations;
     if (host_ms) *host_ms = P->spectrum.host_ms;
     return VIPRS_OK;

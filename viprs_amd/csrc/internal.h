@@ -78,23 +78,50 @@ struct DevEvent {
     ~DevEvent() { if (e) (void)hipEventDestroy(e); }
 };
 
+// The event pair that brackets a feature's kernels on a stream (the sweeps' timing ring never sees them).
+struct EventBracket {
+    DevEvent ev[2];                                // created by the first start()
+    bool timed = false;
+    int start(hipStream_t s) {
+        for (auto& e : ev)
+            if (!e.e) HIP_TRY(hipEventCreate(&e.e));
+        HIP_TRY(hipEventRecord(ev[0].e, s));
+        return VIPRS_OK;
+    }
+    int stop(hipStream_t s) {
+        HIP_TRY(hipEventRecord(ev[1].e, s));
+        timed = true;
+        return VIPRS_OK;
+    }
+    // ms between the last start() and stop(); `nothing`: the error message when nothing has been timed yet
+    int elapsed(int device, double* ms, const char* nothing) {
+        if (!timed) return fail(VIPRS_EINVAL, nothing);
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipEventSynchronize(ev[1].e));
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev[0].e, ev[1].e));
+        *ms = (double)t;
+        return VIPRS_OK;
+    }
+};
+
+struct RidgeBlock;                                 // ridge.h: start and size of an LD block
+
 // ridge solve (abi_ridge.hip, ridge.h): the workspace of a plan, allocated by its first solve and reused by the later ones
 struct RidgeWork {
     bool built = false;
-    DevBuf<char> d_blocks, d_rec;                  // RidgeBlock / RidgeRec per LD block, SNP order
+    DevBuf<char> d_rec;                            // RidgeRec per LD block, SNP order
     DevBuf<int32_t> d_live;                        // blocks still running
     size_t vec_bytes = 0;                          // capacity of each vector below
     DevBuf<char> d_vec[9];                         // v, R v, three residual and three direction vectors in rotation, x
     DevBuf<char> d_shift;
-    DevEvent ev[2];
-    bool timed = false;
+    EventBracket time;
     int iterations = 0;                            // iterations the last solve launched
 };
 
 // extremal eigenvalues (abi_spectrum.hip, lanczos.h): the workspace of a plan, allocated by its first call and reused
 struct SpectrumWork {
     bool built = false;
-    DevBuf<char> d_blocks;                         // RidgeBlock per LD block, SNP order
     DevBuf<double> d_beta;                         // beta_k of the iteration to come, per block
     DevBuf<int32_t> d_status, d_iters;             // per block
     DevBuf<int32_t> d_live;                        // blocks still running
@@ -102,8 +129,7 @@ struct SpectrumWork {
     DevBuf<char> d_vec[3];                         // v, v_prev (w while a step runs), A v
     size_t coef_cap = 0;                           // capacity of each array below (doubles)
     DevBuf<double> d_alpha, d_betas;               // alpha_k / beta_{k+1} at [block * max_iter + k - 1]
-    DevEvent ev[2];
-    bool timed = false;
+    EventBracket time;
     int iterations = 0;                            // iterations the last call launched
     double host_ms = 0.0;                          // host time of its checks (downloads + tridiagonal eigenproblems)
 };
@@ -187,21 +213,20 @@ struct viprs_plan {
     // record and the launch -- occupancy query, team split, launch gate, a scheduler hiccup -- would count as kernel time
     hipEvent_t pending_start_event = nullptr;
     // LD product (abi_dot.hip, ld_dot.h): its own tables over EVERY block of the plan (the product is not filtered by
-    // viprs_plan_set_active_blocks), built by the first product; its own event pair (the sweeps' timing ring never sees it)
+    // viprs_plan_set_active_blocks), built by the first product; its own event pair
     bool dot_built = false;
     viprs::DevBuf<viprs::BlockDesc> d_dot_blocks;  // dense_all_h, then ragged_all_h
     // work lists in the order of the plan's full block lists: (block of d_dot_blocks) << 32 | (first) row of the block; dense [k]: 1 << k rows per item
     viprs::DevBuf<int64_t> d_dot_rows_dense[3], d_dot_rows_ragged;
     viprs::DevBuf<int32_t> d_dot_first;            // upper form with windowed blocks: the first row whose entries reach row j
     viprs::DevBuf<char> d_dot_b, d_dot_y;          // staging of the host-buffer call / the results
-    hipEvent_t ev_dot[2] = {nullptr, nullptr};
-    bool dot_timed = false;
+    viprs::EventBracket time_dot;
     bool unmirrored_wanted = false;                // the last launch that asked for a storage of the upper form wanted the zero lower triangle
     // LD scores (abi_ld_score.hip, ld_score.h): the product's tables; its own staging and event pair
     viprs::DevBuf<char> d_score_a, d_score_y;
     viprs::DevBuf<double> d_score_corr;
-    viprs::DevEvent ev_score[2];
-    bool score_timed = false;
+    viprs::EventBracket time_score;
+    viprs::DevBuf<viprs::RidgeBlock> d_solver_blocks;   // start and size of every LD block, SNP order (ensure_solver_blocks)
     viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
     viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
 
@@ -282,8 +307,11 @@ int team_launch_done(viprs_plan* P);
 // after a synchronisation point: did a team hand-off give up (bounded spin)?
 int check_device_error(viprs_plan* P);
 
-// abi_dot.hip: the tables of the product (every block of the plan, one work item per row), built once per plan
-int build_dot_tables(viprs_plan* P);
+// abi_dot.hip: what every call over the plan's LD rows does first.  The tables of the product (every block of the plan, one
+// work item per row) are built once per plan; an upper-form plan nobody has swept yet is mirrored once
+int prepare_ld_rows(viprs_plan* P);
+// abi_ridge.hip: the block table of the lock-step solvers (P->d_solver_blocks), built once per plan
+int ensure_solver_blocks(viprs_plan* P);
 // abi_dot.hip: the kernels of one LD product on the plan's stream (device pointers, (m, n_cols) column-major), between the
 // product's own two events; nothing is synchronised
 int enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void* dY, double dq_scale, int include_diagonal);

@@ -1,3 +1,4 @@
-#define DOT_U float
-#define DOT_DENSE 1
-#include "launch_ld_dot.inc"
+#define ROWS_U float
+#define ROWS_DENSE 1
+#define ROWS_SCORE 0
+#include "launch_ld_rows.inc"

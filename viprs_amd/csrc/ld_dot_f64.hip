@@ -1,3 +1,4 @@
-#define DOT_U double
-#define DOT_DENSE 0
-#include "launch_ld_dot.inc"
+#define ROWS_U double
+#define ROWS_DENSE 0
+#define ROWS_SCORE 0
+#include "launch_ld_rows.inc"

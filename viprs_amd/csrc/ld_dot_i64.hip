@@ -1,3 +1,4 @@
-#define DOT_U int64_t
-#define DOT_DENSE 0
-#include "launch_ld_dot.inc"
+#define ROWS_U int64_t
+#define ROWS_DENSE 0
+#define ROWS_SCORE 0
+#include "launch_ld_rows.inc"

@@ -1,3 +1,4 @@
-#define SCORE_U int64_t
-#define SCORE_DENSE 0
-#include "launch_ld_score.inc"
+#define ROWS_U int64_t
+#define ROWS_DENSE 0
+#define ROWS_SCORE 1
+#include "launch_ld_rows.inc"
