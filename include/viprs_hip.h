@@ -557,6 +557,55 @@ int viprs_plan_extremal_eigenvalues(viprs_plan* plan, int float_dtype, double dq
 int viprs_plan_last_spectrum_ms(viprs_plan* plan, double* total_ms, int* iterations, double* host_ms /* nullable */);
 int viprs_tridiagonal_extremes(int k, const double* alpha, const double* beta, double* out);
 
+/* ---- genotype scoring: PLINK .bed rows on the device, per-SNP code counts, polygenic scores ------------------------------
+ * What a fitted model is for: score(i, c) = sum_j B[j, c] * dose_j(genotype of sample i at SNP j).  The reference hands this to
+ * plink2 through magenpy (BayesPRSModel.predict -> GWADataLoader.predict); neither is part of the reference tree, so nothing
+ * here claims parity with them: the definition below is this library's own, stated in full.
+ * INPUT.  The rows of a PLINK 1 .bed file in SNP-major mode, WITHOUT the three magic bytes 6C 1B 01 (the reader checks and
+ * strips them): m rows of ceil(n / 4) bytes.  Sample i of SNP j is bits 2 (i % 4) .. 2 (i % 4) + 1 of byte i / 4 of row j.
+ * Codes: 0 = two copies of A1, 1 = missing, 2 = one copy, 3 = no copy.  The unused bits of a row's last byte are arbitrary;
+ * no result depends on them.  1 <= n < 2^31 - 16 or n = 0; offsets into the rows are 64-bit everywhere.
+ *   viprs_genotypes_create       device memory for m rows at a row stride that is a multiple of 16 bytes; every row starts
+ *                                as "all samples missing" until it is uploaded
+ *   viprs_genotypes_upload_rows  rows [first_row, first_row + n_rows) from `bed_rows` (n_rows x ceil(n / 4) bytes, as in the
+ *                                file: a memory-mapped file goes up in slices).  The library then sets every slot at or beyond
+ *                                n of those rows -- the file's own trailing bits and the stride padding -- to code 1
+ *   viprs_genotypes_counts       counts[j][code] = the number of samples i < n with that code, int64, exact, all four codes
+ * SCORE.  `b_host` is (m, n_cols) row-major in T = float32 / float64 (`float_dtype`), `dose_host` the per-SNP dose table
+ * (m, 4) in T indexed by code; dose_host == NULL means {2, 0, 1, 0} for every SNP.  `scores_host` is (n, n_cols) row-major.
+ *   term(i, j, c) = fl_T(B[j][c] * D[j][code(i, j)])                 one rounded multiply, no fma
+ *   P(i, c, k)    = ((0 + term(i, j_k, c)) + term(i, j_k + 1, c)) + ...  plain T additions, SNPs ascending, over chunk
+ *                                                                    k = SNPs [k L, min((k + 1) L, m)), L = VIPRS_SCORE_CHUNK
+ *   score(i, c)   = fl_T(sum_k (double) P(i, c, k))                  double additions from 0, chunks ascending
+ * L is part of the definition.  No floating-point atomics.  A column's bits depend on the genotypes, D and that column only:
+ * not on n_cols, on the other columns, on padding or on how the work was tiled; two calls give identical bits.  Inputs are
+ * finite; behaviour on NaN / inf is unspecified.  (An accumulator that starts at +0 never becomes -0 under these operations,
+ * so leaving out a SNP whose B row is all zeros would be bit-identical; this library does not skip.)
+ * DOSE TABLES are the caller's: additive with missing = 0 is {2, 0, 1, 0}; mean-imputed {2, mu_j, 1, 0} with
+ * mu_j = (2 c0 + c2) / (c0 + c2 + c3) (0 when every sample is missing); standardised {(2 - mu) / s, 0, (1 - mu) / s, -mu / s}
+ * with s_j the population standard deviation of the non-missing doses (a monomorphic SNP: all zeros); alleles swapped
+ * relative to the model: entries 0 and 3 exchanged, mu' = 2 - mu.  Built on the host in double from the exact counts and
+ * rounded once to T (viprs_amd/genotypes.py); the kernel knows only D.
+ * ROUNDING.  |score - exact| <= (L + 2) u_T S + n_chunks 2^-53 S to first order, S = sum_j |B[j][c] D[j][code]|, u_T the unit
+ * roundoff of T: L sequential additions of once-rounded terms, the double sum over the chunks, the final rounding.
+ * Synchronous, on the object's own stream.  The partial sums P of a range of chunks go to a work buffer of bounded size
+ * (at least one chunk: n x n_cols values, at most ~64 MiB otherwise; VIPRS_SCORE_WORK_BYTES in the environment sets another
+ * budget) and a second kernel adds each range to the double sums; the result does not depend on the budget.
+ * Bad dtype code, n_cols < 1, null pointers, rows out of range, n or m < 0: VIPRS_EINVAL before any launch, outputs untouched.
+ * n = 0 or m = 0 is legal: counts and scores are zeros (n = 0: nothing to write).
+ *   viprs_genotypes_last_score_ms   HIP-event time from the first to the last kernel of the last score call on this object
+ *   viprs_genotypes_last_counts_ms  HIP-event time of the counts kernel of the last counts call (its download not included) */
+#define VIPRS_SCORE_CHUNK 1024
+typedef struct viprs_genotypes viprs_genotypes;
+int viprs_genotypes_create(viprs_genotypes** g, int64_t n_samples, int64_t m, int device);
+int viprs_genotypes_upload_rows(viprs_genotypes* g, int64_t first_row, int64_t n_rows, const uint8_t* bed_rows);
+int viprs_genotypes_destroy(viprs_genotypes* g);
+int viprs_genotypes_counts(viprs_genotypes* g, int64_t* counts /* m x 4 */);
+int viprs_genotypes_score(viprs_genotypes* g, int float_dtype, int n_cols, const void* b_host,
+                          const void* dose_host /* m x 4 in T, nullable */, void* scores_host /* n x n_cols */);
+int viprs_genotypes_last_score_ms(viprs_genotypes* g, double* ms);
+int viprs_genotypes_last_counts_ms(viprs_genotypes* g, double* ms);
+
 /* ---- measurement support: synthetic LD generated on the device (bench.py, tests) --------------
  * The "longrange" LD blocks of viprs_amd/utils/synthetic.py (the workload of BASELINE.json's configs, SURVEY.md 8d: the
  * reference gets its LD from magenpy stores, VIPRS.py:151-172, none of which exists here) written straight into a plan's

@@ -131,6 +131,13 @@ _PROTOS = {
     "viprs_plan_extremal_eigenvalues": (_i, [_vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "viprs_plan_last_spectrum_ms": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_i), ctypes.POINTER(_d)]),
     "viprs_tridiagonal_extremes": (_i, [_i, _vp, _vp, _vp]),
+    "viprs_genotypes_create": (_i, [ctypes.POINTER(_vp), _i64, _i64, _i]),
+    "viprs_genotypes_upload_rows": (_i, [_vp, _i64, _i64, _vp]),
+    "viprs_genotypes_destroy": (_i, [_vp]),
+    "viprs_genotypes_counts": (_i, [_vp, _vp]),
+    "viprs_genotypes_score": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "viprs_genotypes_last_score_ms": (_i, [_vp, ctypes.POINTER(_d)]),
+    "viprs_genotypes_last_counts_ms": (_i, [_vp, ctypes.POINTER(_d)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

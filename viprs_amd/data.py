@@ -90,12 +90,26 @@ class SumstatsArrays:
 class ArrayDataLoader:
     """Minimal ``GWADataLoader`` look-alike: ``ld`` / ``sumstats_table`` dicts keyed by chromosome."""
 
-    def __init__(self, ld, sumstats, n=None):
+    def __init__(self, ld, sumstats, n=None, genotype=None, phenotype=None, snp_table=None, device=0):
+        """`genotype`: None, or ``{chromosome: DeviceGenotypes | HostGenotypes | (packed_rows, n) | .bed prefix}`` (opened at
+        the first `predict`; a prefix also supplies the chromosome's SNP table and, when none is given, the phenotype).
+        `phenotype`: (n_samples,) values of the genotyped samples.  `snp_table`: ``{chromosome: {"SNP", "A1", "A2", ...}}``
+        arrays per SNP -- of the genotypes when there are any, else of the summary statistics; what `predict` of a model
+        aligns by.  `ld` / `sumstats` may be empty dicts for a loader that only carries genotypes."""
         self.ld = dict(ld)
         self.sumstats_table = dict(sumstats)
-        self.genotype = None
+        self.genotype = dict(genotype) if genotype is not None else None
+        self.phenotype = None if phenotype is None else np.asarray(phenotype, dtype=np.float64)
+        self.snp_table = {c: dict(t) for c, t in snp_table.items()} if snp_table else None
+        self.device = int(device)
+        self._own_genotypes = []
         self.shapes = {c: int(s.n_per_snp.shape[0]) for c, s in self.sumstats_table.items()}
-        self.n = float(n) if n is not None else float(max(s.n_per_snp.max() for s in self.sumstats_table.values()))
+        if n is not None:
+            self.n = float(n)
+        elif self.sumstats_table:
+            self.n = float(max(s.n_per_snp.max() for s in self.sumstats_table.values()))
+        else:
+            self.n = None
 
     @property
     def chromosomes(self):
@@ -108,10 +122,77 @@ class ArrayDataLoader:
     def get_ld_matrices(self):
         return self.ld
 
+    # ---- genotypes: polygenic scores of the loader's samples (magenpy's ``GWADataLoader.predict``) ----
+    def _open_genotypes(self, c):
+        """The genotypes of chromosome `c`, opened once (`viprs_amd.genotypes.open_genotypes`)."""
+        from .genotypes import _Genotypes, open_genotypes
+        g = self.genotype[c]
+        if not isinstance(g, _Genotypes):
+            g, owned, bed = open_genotypes(g, device=self.device)
+            self.genotype[c] = g
+            if owned:
+                self._own_genotypes.append(g)
+            if bed is not None:
+                if self.snp_table is None or c not in self.snp_table:
+                    self.snp_table = dict(self.snp_table or {})
+                    self.snp_table[c] = bed[2]
+                if self.phenotype is None and not np.all(np.isnan(bed[3])):
+                    self.phenotype = bed[3]
+        return g
+
+    @property
+    def n_samples(self):
+        """Genotyped samples (None without genotypes)."""
+        if not self.genotype:
+            return None
+        return int(self._open_genotypes(sorted(self.genotype)[0]).n)
+
+    def predict(self, beta_by_chromosome, swapped=None, dose="mean", float_precision=None, per_chromosome=False):
+        """Polygenic scores of the genotyped samples: every chromosome of `beta_by_chromosome` (``(m_c,)`` or
+        ``(m_c, n_models)`` effects per copy of A1) is scored on its genotypes (`DeviceGenotypes.score`; on the host without a
+        device) in `float_precision` (default: the effects' own), and the chromosomes are added on the host in double in
+        ascending chromosome order: ``(n,)`` or ``(n, n_models)`` float64.  `dose`: a mode of
+        `viprs_amd.genotypes.dose_table` or None (additive, missing = 0); `swapped`: None or ``{chromosome: (m_c,) mask}``
+        of the SNPs whose A1 / A2 are exchanged relative to the effects.  `per_chromosome`: the ``{chromosome: scores}``
+        (float64) dict instead of the sum."""
+        if self.genotype is None:
+            raise ValueError("this loader holds no genotypes.  Remedy: ArrayDataLoader(..., genotype={chromosome: "
+                             ".bed prefix | (packed_rows, n) | DeviceGenotypes}).")
+        parts = {}
+        for c in sorted(beta_by_chromosome):
+            if c not in self.genotype:
+                raise ValueError(f"chromosome {c} of the effects has no genotypes in this loader")
+            g = self._open_genotypes(c)
+            b = np.asarray(beta_by_chromosome[c])
+            if b.shape[0] != g.m:
+                raise ValueError(f"chromosome {c}: {b.shape[0]} effects against {g.m} genotyped SNPs (give both loaders "
+                                 "SNP tables to have them aligned by SNP id)")
+            sw = None if swapped is None else swapped.get(c)
+            table = None if dose is None and sw is None else g.dose_table(
+                dose or "zero", swapped=sw, dtype=float_precision or (b.dtype if b.dtype == np.float64 else np.float32))
+            parts[c] = np.asarray(g.score(b, dose=table, float_precision=float_precision), dtype=np.float64)
+        if not parts:
+            raise ValueError("no effects were given")
+        if per_chromosome:
+            return parts
+        total = None
+        for c in sorted(parts):
+            total = parts[c].copy() if total is None else total + parts[c]
+        return total
+
+    def close_genotypes(self):
+        for g in self._own_genotypes:
+            g.close()
+        self._own_genotypes = []
+
     def split_by_chromosome(self):
         """One loader per chromosome, as magenpy's ``GWADataLoader.split_by_chromosome()`` hands to the reference's
         per-chromosome fits (bin/viprs_fit:232-238)."""
-        return {c: ArrayDataLoader({c: self.ld[c]}, {c: self.sumstats_table[c]}) for c in self.chromosomes}
+        return {c: ArrayDataLoader({c: self.ld[c]}, {c: self.sumstats_table[c]},
+                                   genotype=None if self.genotype is None or c not in self.genotype else {c: self.genotype[c]},
+                                   phenotype=self.phenotype, device=self.device,
+                                   snp_table=None if not self.snp_table or c not in self.snp_table else {c: self.snp_table[c]})
+                for c in self.chromosomes}
 
     @classmethod
     def synthetic(cls, chrom_sizes, ld_dtype=np.float32, seed=7209, n=1e5, forms=("symmetric", "upper"), h2=0.2,

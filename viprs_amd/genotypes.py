@@ -1,0 +1,324 @@
+"""Genotypes on the device: packed PLINK .bed rows, per-SNP code counts, dose tables and polygenic scores.
+
+The reference turns posterior effect sizes into scores through magenpy and plink2 (``BayesPRSModel.predict`` ->
+``GWADataLoader.predict``); neither is part of the reference tree, so nothing here claims parity with them.  The definition
+is stated in full in ``include/viprs_hip.h`` (viprs_genotypes_*):
+
+    score[i, c] = sum_j B[j, c] * D[j, code(i, j)]
+
+with ``code`` the 2-bit .bed code (0 = two copies of A1, 1 = missing, 2 = one copy, 3 = no copy) and ``D`` a per-SNP dose
+table indexed by the code.  Everything a user means by "additive", "mean-imputed", "standardised" or "alleles swapped" is a
+dose table, built here on the host in double from the exact counts and rounded once to the scoring precision.
+
+* ``score_host``         NumPy float64 straight from the definition: the CPU fallback and the base of the tests;
+* ``dose_table``         the tables from the counts;
+* ``DeviceGenotypes``    the rows on a HIP device (`viprs_genotypes_*`): ``counts``, ``dose_table``, ``score``;
+* ``HostGenotypes``      the same surface over `score_host` (what a loader uses when no device is visible);
+* ``open_genotypes``     a loader's genotype entry -- one of the two above, ``(packed_rows, n)`` or a .bed prefix -- opened;
+* ``model_predict``      ``predict()`` of the model classes.
+"""
+import ctypes
+
+import numpy as np
+
+from .io.plink_bed import bytes_per_row, read_bed, unpack_codes
+
+SCORE_CHUNK = 1024                       # VIPRS_SCORE_CHUNK (include/viprs_hip.h): part of the definition of the device sum
+ADDITIVE = (2.0, 0.0, 1.0, 0.0)          # the dose table of a NULL `dose`
+DOSE_MODES = ("mean", "zero", "standardize")
+_HOST_SLAB = 2048                        # SNPs `score_host` unpacks at a time
+
+
+def _check_rows(packed_rows, n):
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must not be negative")
+    p = packed_rows if isinstance(packed_rows, np.ndarray) else np.asarray(packed_rows)
+    if p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != bytes_per_row(n):
+        raise ValueError(f"packed rows: an (m, {bytes_per_row(n)}) uint8 array for n = {n}, got {p.dtype} {p.shape}")
+    return p, n
+
+
+def counts_host(packed_rows, n):
+    """(m, 4) int64: the samples ``i < n`` of every SNP per code."""
+    p, n = _check_rows(packed_rows, n)
+    out = np.zeros((p.shape[0], 4), dtype=np.int64)
+    for a in range(0, p.shape[0], _HOST_SLAB):
+        codes = unpack_codes(p[a:a + _HOST_SLAB], n)
+        for k in range(4):
+            out[a:a + _HOST_SLAB, k] = (codes == k).sum(axis=1)
+    return out
+
+
+def dose_table(counts, mode="mean", swapped=None, dtype=np.float32):
+    """The (m, 4) dose table of `mode` from the exact (m, 4) code counts, computed in double and rounded once to `dtype`.
+
+    ``"zero"``         additive, missing = 0: ``{2, 0, 1, 0}``
+    ``"mean"``         mean-imputed: ``{2, mu, 1, 0}``, ``mu = (2 c0 + c2) / (c0 + c2 + c3)`` (0 when every sample is missing)
+    ``"standardize"``  ``{(2 - mu) / s, 0, (1 - mu) / s, -mu / s}``, ``s`` the population standard deviation of the non-missing
+                       doses; a monomorphic SNP (and one without any sample) gets an all-zero table
+    `swapped`: None or an (m,) boolean mask of the SNPs whose A1 / A2 are exchanged relative to the effect sizes: entries 0
+    and 3 change places and ``mu' = 2 - mu``.  Exact -- not a sign flip of the effect, which would change every score by a
+    constant."""
+    if mode not in DOSE_MODES:
+        raise ValueError(f"dose mode {mode!r}: one of {DOSE_MODES}")
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+    m = c.shape[0]
+    sw = np.zeros(m, dtype=bool) if swapped is None else np.asarray(swapped, dtype=bool).reshape(m)
+    # copies of the allele the effect sizes count: A1, or A2 where swapped
+    c_two = np.where(sw, c[:, 3], c[:, 0]).astype(np.float64)
+    c_one = c[:, 2].astype(np.float64)
+    c_none = np.where(sw, c[:, 0], c[:, 3]).astype(np.float64)
+    nn = c_two + c_one + c_none
+    some = nn > 0
+    mu = np.where(some, (2.0 * c_two + c_one) / np.where(some, nn, 1.0), 0.0)
+    D = np.zeros((m, 4), dtype=np.float64)              # columns: dose of two copies, missing, one copy, no copy
+    if mode == "zero":
+        D[:, 0], D[:, 2] = 2.0, 1.0
+    elif mode == "mean":
+        D[:, 0], D[:, 1], D[:, 2] = 2.0, mu, 1.0
+    else:
+        poly = some & (np.maximum(np.maximum(c_two, c_one), c_none) < nn)
+        var = (c_two * (2.0 - mu) ** 2 + c_one * (1.0 - mu) ** 2 + c_none * mu ** 2) / np.where(some, nn, 1.0)
+        sd = np.sqrt(np.where(poly, var, 1.0))
+        D[:, 0], D[:, 2], D[:, 3] = (2.0 - mu) / sd, (1.0 - mu) / sd, -mu / sd
+        D[~poly] = 0.0
+    D[sw] = D[sw][:, [3, 1, 2, 0]]
+    return np.ascontiguousarray(D.astype(dtype))
+
+
+def score_host(packed_rows, n, B, D=None):
+    """``score[i, c] = sum_j B[j, c] D[j, code(i, j)]`` in float64: ``(n,)`` for ``(m,)`` effects, ``(n, n_cols)`` for
+    ``(m, n_cols)``.  `D`: an (m, 4) dose table or None (``{2, 0, 1, 0}``).  Nothing depends on the trailing bits of a row."""
+    p, n = _check_rows(packed_rows, n)
+    B = np.asarray(B)
+    m = p.shape[0]
+    B2 = B.reshape(m, B.shape[1] if B.ndim == 2 else 1).astype(np.float64)
+    Dm = np.broadcast_to(np.array(ADDITIVE), (m, 4)) if D is None else np.asarray(D, dtype=np.float64).reshape(m, 4)
+    out = np.zeros((n, B2.shape[1]), dtype=np.float64)
+    for a in range(0, m, _HOST_SLAB):
+        codes = unpack_codes(p[a:a + _HOST_SLAB], n)
+        X = np.take_along_axis(Dm[a:a + _HOST_SLAB], codes.astype(np.intp), axis=1)       # (slab, n) doses
+        out += X.T @ B2[a:a + _HOST_SLAB]
+    return out[:, 0] if B.ndim == 1 else out
+
+
+class _Genotypes:
+    """What the two genotype classes share: everything that follows from the counts."""
+
+    n = m = 0
+
+    def counts(self):
+        raise NotImplementedError
+
+    def allele_frequency(self):
+        """Frequency of A1 among the non-missing samples, (m,) float64 (NaN where every sample is missing)."""
+        c = self.counts().astype(np.float64)
+        nn = c[:, 0] + c[:, 2] + c[:, 3]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (2.0 * c[:, 0] + c[:, 2]) / (2.0 * nn)
+
+    def dose_table(self, mode="mean", swapped=None, dtype=np.float32):
+        return dose_table(self.counts(), mode, swapped, dtype)
+
+    def _score_args(self, B, dose, float_precision):
+        B = np.asarray(B)
+        if float_precision is None:
+            float_precision = B.dtype if B.dtype in (np.float32, np.float64) else np.float32
+        T = np.dtype(float_precision)
+        if T not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"float_precision: float32 or float64, got {T}")
+        if B.ndim not in (1, 2) or B.shape[0] != self.m or (B.ndim == 2 and B.shape[1] < 1):
+            raise ValueError(f"effects: ({self.m},) or ({self.m}, n_cols), got {B.shape}")
+        B2 = np.ascontiguousarray(B.reshape(self.m, B.shape[1] if B.ndim == 2 else 1), dtype=T)
+        if dose is None or isinstance(dose, str):
+            D = None if dose is None else self.dose_table(dose, dtype=T)
+        else:
+            D = np.ascontiguousarray(dose, dtype=T)
+            if D.shape != (self.m, 4):
+                raise ValueError(f"dose table: ({self.m}, 4), got {D.shape}")
+        return B2, D, T, B.ndim == 1
+
+
+class HostGenotypes(_Genotypes):
+    """`DeviceGenotypes`' surface on the host (`counts_host`, `score_host`): scores are float64 sums rounded to the asked
+    precision."""
+
+    def __init__(self, packed_rows, n):
+        self.rows, self.n = _check_rows(packed_rows, n)
+        self.m = int(self.rows.shape[0])
+        self._counts = None
+
+    def counts(self):
+        if self._counts is None:
+            self._counts = counts_host(self.rows, self.n)
+        return self._counts
+
+    def score(self, B, dose=None, float_precision=None):
+        B2, D, T, flat = self._score_args(B, dose, float_precision)
+        s = score_host(self.rows, self.n, B2, D).astype(T)
+        return s[:, 0] if flat else s
+
+    def close(self):
+        pass
+
+
+class DeviceGenotypes(_Genotypes):
+    """Packed .bed rows of one chromosome (or any set of SNPs) resident on a HIP device.
+
+    `packed_rows`: (m, ceil(n / 4)) uint8, e.g. `read_bed`'s memory map -- uploaded in slices of `slice_bytes`, never
+    unpacked on the host."""
+
+    def __init__(self, packed_rows, n, device=0, slice_bytes=256 << 20):
+        from . import _lib as L
+        self._L = L
+        rows, self.n = _check_rows(packed_rows, n)
+        self.m = int(rows.shape[0])
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        self._counts = None
+        L.check(L.lib.viprs_genotypes_create(ctypes.byref(self._h), self.n, self.m, self.device))
+        bpr = bytes_per_row(self.n)
+        step = max(1, int(slice_bytes) // max(bpr, 1))
+        for a in range(0, self.m if bpr else 0, step):
+            part = np.ascontiguousarray(rows[a:a + step])
+            L.check(L.lib.viprs_genotypes_upload_rows(self._h, a, part.shape[0], part.ctypes.data_as(ctypes.c_void_p)))
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ValueError("DeviceGenotypes is closed")
+        return self._h
+
+    def counts(self):
+        """(m, 4) int64 code counts of the samples ``i < n`` (`viprs_genotypes_counts`; kept after the first call)."""
+        if self._counts is None:
+            c = np.zeros((self.m, 4), dtype=np.int64)
+            self._L.check(self._L.lib.viprs_genotypes_counts(self.handle, c.ctypes.data_as(ctypes.c_void_p)))
+            self._counts = c
+        return self._counts
+
+    def score(self, B, dose=None, float_precision=None):
+        """Scores of the ``(m,)`` / ``(m, n_cols)`` effects `B`: ``(n,)`` / ``(n, n_cols)`` in `float_precision` (default:
+        B's own when it is float32 / float64, else float32), in the order `include/viprs_hip.h` defines.  `dose`: None (the
+        additive table ``{2, 0, 1, 0}``, no table is uploaded), a mode of `dose_table`, or an (m, 4) table."""
+        B2, D, T, flat = self._score_args(B, dose, float_precision)
+        out = np.zeros((self.n, B2.shape[1]), dtype=T)
+        L = self._L
+        L.check(L.lib.viprs_genotypes_score(self.handle, L.F32 if T == np.float32 else L.F64, B2.shape[1],
+                                            B2.ctypes.data_as(ctypes.c_void_p),
+                                            None if D is None else D.ctypes.data_as(ctypes.c_void_p),
+                                            out.ctypes.data_as(ctypes.c_void_p)))
+        return out[:, 0] if flat else out
+
+    def last_score_ms(self):
+        """HIP-event time (ms) of the kernels of the last `score` on this object."""
+        ms = ctypes.c_double(0.0)
+        self._L.check(self._L.lib.viprs_genotypes_last_score_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
+    def last_counts_ms(self):
+        """HIP-event time (ms) of the counts kernel of the last device `counts` on this object (no download)."""
+        ms = ctypes.c_double(0.0)
+        self._L.check(self._L.lib.viprs_genotypes_last_counts_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._L.lib.viprs_genotypes_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def open_genotypes(entry, device=0):
+    """A loader's genotype entry opened: -> ``(genotypes, owned, bed)``.  `entry`: a `DeviceGenotypes` / `HostGenotypes`
+    (returned as it is), ``(packed_rows, n)``, or the prefix of a .bed / .bim / .fam triple.  New objects live on HIP device
+    `device`, or on the host when no device is visible; `owned` says the caller closes them; `bed`: None or what `read_bed`
+    returned for a prefix."""
+    if isinstance(entry, _Genotypes):
+        return entry, False, None
+    bed = None
+    if isinstance(entry, (str, bytes)) or hasattr(entry, "__fspath__"):
+        bed = read_bed(entry)
+        entry = bed[:2]
+    rows, n = entry
+    from . import _lib
+    if _lib.device_count() < 1:
+        return HostGenotypes(rows, n), True, bed
+    return DeviceGenotypes(rows, n, device=device), True, bed
+
+
+# ---- predict() of the model classes ---------------------------------------------------------------------------------------
+def _align(model_table, test_table, beta, c):
+    """Effects of the model's SNPs laid out over the test table's SNPs by SNP id: absent SNPs score 0, SNPs whose A1 / A2
+    are exchanged are marked as swapped, any other allele pair is dropped.  -> (beta over the test SNPs, swapped mask)."""
+    for t, who in ((model_table, "the model's loader"), (test_table, "the test loader")):
+        if any(k not in t for k in ("SNP", "A1", "A2")):
+            raise ValueError(f"chromosome {c}: the SNP table of {who} needs the columns SNP, A1 and A2")
+    ids = np.asarray(model_table["SNP"], dtype=str)
+    if ids.shape[0] != beta.shape[0]:
+        raise ValueError(f"chromosome {c}: the model's SNP table has {ids.shape[0]} SNPs, its effects {beta.shape[0]}")
+    t_ids = np.asarray(test_table["SNP"], dtype=str)
+    for who, v in (("the model's loader", ids), ("the test loader", t_ids)):
+        u, n_of = np.unique(v, return_counts=True)
+        if np.any(n_of > 1):
+            raise ValueError(f"chromosome {c}: the SNP table of {who} lists {u[n_of > 1][0]!r} more than once "
+                             f"({int(np.sum(n_of > 1))} duplicated ids): the alignment by SNP id needs unique ids")
+    where = {s: k for k, s in enumerate(ids)}
+    at = np.array([where.get(s, -1) for s in t_ids], dtype=np.int64)
+    found = at >= 0
+    a1m, a2m = np.asarray(model_table["A1"], dtype=str)[at[found]], np.asarray(model_table["A2"], dtype=str)[at[found]]
+    a1t, a2t = np.asarray(test_table["A1"], dtype=str)[found], np.asarray(test_table["A2"], dtype=str)[found]
+    same = (a1m == a1t) & (a2m == a2t)
+    swap = (a1m == a2t) & (a2m == a1t) & ~same
+    out = np.zeros((t_ids.shape[0],) + beta.shape[1:], dtype=beta.dtype)
+    rows = np.nonzero(found)[0]
+    keep = same | swap
+    out[rows[keep]] = beta[at[found][keep]]
+    swapped = np.zeros(t_ids.shape[0], dtype=bool)
+    swapped[rows[swap]] = True
+    return out, swapped
+
+
+def model_predict(model, test_gdl=None, per_chromosome=False, **kw):
+    """``BayesPRSModel.predict`` (viprs/model/BayesPRSModel.py:229-250): the polygenic scores of the training loader's samples,
+    or of `test_gdl`'s, from the model's posterior mean effects -- ``(n,)``, or ``(n, n_models)`` for a grid.  A `test_gdl`
+    with SNP tables (and a model whose loader has them) is aligned by SNP id (`_align`); without tables the SNP counts must
+    agree.  `per_chromosome`: ``{chromosome: scores}`` instead of their sum.  `kw` goes to the loader's ``predict``."""
+    beta = getattr(model, "post_mean_beta", None)
+    if beta is None:
+        raise ValueError("The posterior means for BETA are not set. Call `.fit()` first.")
+    gdl = model.gdl if test_gdl is None else test_gdl
+    if getattr(gdl, "genotype", None) is None:
+        raise ValueError("The data loader holds no genotypes: predict() needs them.  Remedy: build the loader with "
+                         "ArrayDataLoader(..., genotype={chromosome: bed prefix | (packed_rows, n) | DeviceGenotypes}).")
+    if not hasattr(gdl, "predict"):
+        raise TypeError(f"{type(gdl).__name__} has no predict(beta_by_chromosome)")
+    beta = {c: np.asarray(b) for c, b in beta.items()}
+    swapped = None
+    if hasattr(gdl, "_open_genotypes"):                        # (a .bed prefix brings its SNP table when it is opened)
+        for c in sorted(gdl.genotype):
+            gdl._open_genotypes(c)
+    test_tables = getattr(gdl, "snp_table", None) if test_gdl is not None else None
+    model_tables = getattr(model.gdl, "snp_table", None)
+    if test_tables and model_tables:
+        # every chromosome of the effects needs genotypes and both SNP tables, as on the path without tables
+        aligned, swapped = {}, {}
+        for c in sorted(beta):
+            if c not in gdl.genotype:
+                raise ValueError(f"chromosome {c} of the effects has no genotypes in the test loader")
+            if c not in test_tables:
+                raise ValueError(f"chromosome {c} of the test loader has genotypes but no SNP table")
+            if c not in model_tables:
+                raise ValueError(f"chromosome {c} of the effects has no SNP table in the model's loader")
+            aligned[c], swapped[c] = _align(model_tables[c], test_tables[c], beta[c], c)
+        beta = aligned
+    from .data import ArrayDataLoader
+    if not isinstance(gdl, ArrayDataLoader):
+        return gdl.predict(beta)                               # a foreign loader: the reference's call
+    return gdl.predict(beta, swapped=swapped, per_chromosome=per_chromosome, **kw)

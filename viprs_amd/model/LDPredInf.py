@@ -126,6 +126,12 @@ class LDPredInf:
     def get_posterior_mean_beta(self):
         return self.post_mean_beta
 
+    def predict(self, test_gdl=None, **kw):
+        """Polygenic scores of the training loader's genotyped samples, or of `test_gdl`'s (BayesPRSModel.py:229-250):
+        `viprs_amd.genotypes.model_predict`."""
+        from ..genotypes import model_predict
+        return model_predict(self, test_gdl, **kw)
+
     def fit(self, solver="minres", rtol=None, maxiter=None, x0=None, **solver_kwargs):
         """Solves ``(R + lam I) beta = beta_hat`` with ``lam = M / (N h2)`` (LDPredInf.py:81-86) for the standardised
         effects.  `x0`: a start vector, ``{chromosome: array}`` or one array over all SNPs."""

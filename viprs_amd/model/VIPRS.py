@@ -658,6 +658,14 @@ class VIPRS:
             tables[c] = pd.concat([tables[c], pd.DataFrame(add, index=tables[c].index)], axis=1)
         return tables if per_chromosome else pd.concat([tables[c] for c in chroms])
 
+    def predict(self, test_gdl=None, **kw):
+        """Polygenic scores from the posterior mean effects (BayesPRSModel.py:229-250): of the training loader's genotyped
+        samples, or of `test_gdl`'s -- ``(n,)``, one column per grid model ``(n, n_models)`` for a fitted grid.  ValueError
+        before `fit()` and for a loader without genotypes.  The scoring runs on the device (`DeviceGenotypes.score`; on the
+        host without one); SNP alignment, `per_chromosome` and `dose`: `viprs_amd.genotypes.model_predict`."""
+        from ..genotypes import model_predict
+        return model_predict(self, test_gdl, **kw)
+
     def pseudo_validate(self, validation_std_beta=None, validation_ld=None):
         """Pseudo-R^2 of the fitted effects against standardized marginal betas of an independent
         cohort: (r'b)^2 / (b'Rb), one value per model for grid fits.

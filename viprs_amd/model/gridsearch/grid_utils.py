@@ -1,7 +1,8 @@
 """Model selection / averaging over a fitted ``VIPRSGrid`` (viprs/model/gridsearch/grid_utils.py).
 
-``select_best_model`` supports the ELBO and the pseudo-validation criteria; the `validation` criterion of the
-reference needs its genotype prediction stack (out of scope).  Deviation, on purpose: models are ranked by
+``select_best_model`` supports the reference's three criteria: the ELBO, pseudo-validation from summary statistics, and
+`validation` -- the R^2 of every model's polygenic score (``predict`` on the validation loader's genotypes: on the device,
+`viprs_amd.genotypes`) against the validation loader's phenotype (grid_utils.py:43-55).  Deviation, on purpose: models are ranked by
 their own final ELBOs (``VIPRSGrid.model_elbos`` = the ``ELBO`` column of ``validation_result``).  The
 reference calls ``VIPRS.elbo()`` on the (m, n_models) arrays (grid_utils.py:38), which sums the
 variational terms over ALL models and therefore only differs between models through the
@@ -12,22 +13,63 @@ import copy
 import numpy as np
 
 
+def _validation_phenotype(validation_gdl):
+    """The validation loader's genotypes and phenotype checked (grid_utils.py:45-47) -> (n,) float64 phenotype."""
+    if validation_gdl is None:
+        raise ValueError("criterion='validation' needs `validation_gdl`: a data loader with the validation samples' "
+                         "genotypes and phenotype (ArrayDataLoader(..., genotype=..., phenotype=...)).")
+    if getattr(validation_gdl, "genotype", None) is None:
+        raise ValueError("criterion='validation': the validation loader holds no genotypes.  Remedy: "
+                         "ArrayDataLoader(..., genotype={chromosome: .bed prefix | (packed_rows, n) | DeviceGenotypes}).")
+    y = getattr(validation_gdl, "phenotype", None)
+    if y is None:
+        y = getattr(getattr(validation_gdl, "sample_table", None), "phenotype", None)
+    if y is None and hasattr(validation_gdl, "_open_genotypes"):      # a .bed prefix brings the .fam phenotype with it
+        for c in sorted(validation_gdl.genotype):
+            validation_gdl._open_genotypes(c)
+        y = validation_gdl.phenotype
+    if y is None:
+        raise ValueError("criterion='validation': the validation loader has no phenotype.  Remedy: "
+                         "ArrayDataLoader(..., phenotype=<(n_samples,) array>), or a .fam file with a phenotype column.")
+    return np.asarray(y, dtype=np.float64)
+
+
+def _validation_r2(prs, y):
+    """R^2 of every column of `prs` against `y` over the samples whose phenotype is known (a .fam file writes a missing
+    phenotype as -9 or NA: NaN here); non-finite values count as 0."""
+    from ...eval.continuous_metrics import r2
+    if np.ndim(prs) < 1 or np.shape(prs)[0] != y.shape[0]:
+        raise ValueError(f"criterion='validation': {y.shape[0]} phenotypes against scores of shape {np.shape(prs)}")
+    prs = np.asarray(prs, dtype=np.float64).reshape(y.shape[0], -1)
+    known = np.isfinite(y)
+    if np.sum(known) < 3:
+        raise ValueError(f"criterion='validation': only {int(np.sum(known))} of {y.shape[0]} validation samples have a "
+                         "phenotype.  Remedy: ArrayDataLoader(..., phenotype=<(n_samples,) array>).")
+    y, prs = y[known], prs[known]
+    return np.nan_to_num(np.array([r2(y, prs[:, i]) for i in range(prs.shape[1])]), nan=0.0, neginf=0.0, posinf=0.0)
+
+
 def select_best_model(viprs_grid_model, validation_gdl=None, criterion="ELBO", validation_ld=None):
     """grid_utils.py:8-100.  `pseudo_validation`: the model with the highest summary-statistics pseudo-R^2 on
     held-out standardized betas -- `validation_gdl` may be a `{chromosome: std_beta}` dict (or an object with
-    that dict as `.std_beta`); otherwise `viprs_grid_model.validation_std_beta` is used.  `validation_ld` (a
+    that dict as `.std_beta`); otherwise `viprs_grid_model.validation_std_beta` is used.  `validation`: the model with the
+    highest R^2 of its polygenic score on `validation_gdl`'s genotypes against `validation_gdl.phenotype`
+    (``validation_result["Validation_R2"]``; non-finite values count as 0).  `validation_ld` (a
     `{chromosome: LDPlan}` dict, or of `(left_bound, indptr, data, low_memory)` tuples) scores the models against the LD of
     an external validation panel instead of the training LD (`VIPRS.pseudo_validate`)."""
     if criterion not in ("ELBO", "validation", "pseudo_validation"):
         raise AssertionError(f"unknown criterion {criterion!r}")
-    if criterion == "validation":
-        raise NotImplementedError("the genotype-based validation criterion needs the reference's prediction stack")
     m = viprs_grid_model
+    if criterion == "validation":
+        y = _validation_phenotype(validation_gdl)
     ok = m.valid_terminated_models
     if np.sum(ok) < 2:
         raise ValueError("Less than two models converged successfully. Cannot perform model selection.")
     if criterion == "ELBO":
         score = np.array(m.model_elbos, dtype=np.float64)
+    elif criterion == "validation":
+        score = _validation_r2(m.predict(test_gdl=validation_gdl), y)
+        m.validation_result["Validation_R2"] = score
     else:
         vb = validation_gdl if isinstance(validation_gdl, dict) else getattr(validation_gdl, "std_beta", None)
         if vb is None:
@@ -115,12 +157,15 @@ def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO
     """`select_best_model` per chromosome of a fitted ``VIPRSGridPerChromosome`` or ``VIPRSGridPathwisePerChromosome``: every
     chromosome keeps ITS best grid point, the model ends in ``VIPRSPerChromosome``'s result layout (``pi[c]`` ... scalars,
     ``pip[c]`` ... of shape (m_c,), ``optim_results[c]`` one result, ``best_model_idx[c]``).  What `select_best_model` picks
-    on each chromosome's own ``VIPRSGrid`` fit, the same arrays.  `validation_ld`: as in `select_best_model`."""
+    on each chromosome's own ``VIPRSGrid`` fit, the same arrays.  `validation_ld`: as in `select_best_model`.  `validation`:
+    every chromosome's grid is ranked by the R^2 of the score of that chromosome's SNPs (``validation_result[c]["Validation_R2"]``)."""
     if criterion not in ("ELBO", "validation", "pseudo_validation"):
         raise AssertionError(f"unknown criterion {criterion!r}")
-    if criterion == "validation":
-        raise NotImplementedError("the genotype-based validation criterion needs the reference's prediction stack")
     m = model
+    if criterion == "validation":
+        # every chromosome's grid is ranked by the score of THAT chromosome's SNPs alone
+        y = _validation_phenotype(validation_gdl)
+        prs = m.predict(test_gdl=validation_gdl, per_chromosome=True)
     best = {}
     for c in m.groups:
         ok = np.array([r.valid_optim_result for r in m.optim_results[c]])
@@ -128,6 +173,11 @@ def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO
             raise ValueError(f"chromosome {c}: less than two models converged successfully. Cannot perform model selection.")
         if criterion == "ELBO":
             score = np.array(m.model_elbos[c], dtype=np.float64)
+        elif criterion == "validation":
+            if c not in prs:
+                raise ValueError(f"chromosome {c}: the validation loader has no genotypes for it")
+            score = _validation_r2(prs[c], y)
+            m.validation_result[c]["Validation_R2"] = score
         else:
             vb = validation_gdl if isinstance(validation_gdl, dict) else getattr(validation_gdl, "std_beta", None)
             if vb is None:
