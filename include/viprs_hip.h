@@ -381,7 +381,9 @@ int viprs_device_synchronize(int device);
  * this plan, measured on the stream they were launched on.  `which`: 0 = all kernels of the
  * sweep, 1 = dominant (panel) kernel only, 2 = HOST time the library spent between recording that
  * kernel's start event and recording its end event (the launch call: a start event recorded into
- * an empty stream is reached at once, so host time spent there counts into the event bracket). */
+ * an empty stream is reached at once, so host time spent there counts into the event bracket).
+ * A sweep that brackets no dominant kernel -- a spike-and-slab sweep over windowed blocks only -- reports
+ * 0 for `which` = 1 and 2, whatever the sweeps before it did.                                   */
 int viprs_plan_last_kernel_ms(viprs_plan* plan, int which, double* ms);
 /* Every sweep records its HIP events into a ring of 256 entries.  `timing_reset` forgets them;
  * `timing_history` returns the durations (ms) of the most recent min(capacity, 256, recorded)
@@ -395,6 +397,35 @@ int viprs_plan_timing_history(viprs_plan* plan, int which, double* ms, int capac
 int viprs_plan_last_math_modes(const viprs_plan* plan, int* mask);
 /* Number of SNPs of the last sweep that took the skip branch (e_step.hpp:410-413).            */
 int viprs_plan_last_skipped(viprs_plan* plan, int64_t* n_skipped);
+/* The route of a sweep (pure host code; usable without a GPU): which kernel family a configuration takes and which HIP
+ * events the sweep records.  In: the state's precision, model kind and width (K or G), the LD element type, whether the
+ * plan's active dense / windowed block lists are non-empty, and three switches -- `band_ok`: VIPRS_BAND is not 0, the LD
+ * type is fp32 / int8 / int16 and the widest window fits the band kernel's q ring; `grid_mfma`: the batched grid kernel is
+ * on (VIPRS_GRID_MFMA, or by default enough dense blocks to fill the chip); `f64_row_by_row`: VIPRS_F64_ROW_BY_ROW is set.
+ * Out: `route[VIPRS_ROUTE_COUNT]`.  VIPRS_EINVAL with the launcher's message when the family the configuration leads to
+ * has no instantiation for the LD element type.                                                                       */
+enum viprs_sweep_family {
+    VIPRS_FAMILY_NONE = 0,           /* no launcher is called for the list */
+    VIPRS_FAMILY_GENERIC = 1,        /* row-by-row kernels (called for an empty list too: they return at once) */
+    VIPRS_FAMILY_TILE_F64 = 2,       /* float64 states: the panel-walking kernels (likewise) */
+    VIPRS_FAMILY_PANEL = 3,          /* the panel sweep; model 0 spike-and-slab, 1 grid column, 2 mixture K <= 8, 3 mixture K <= 31 */
+    VIPRS_FAMILY_BAND = 4,           /* band kernel of the windowed blocks; model 0 spike-and-slab, 1 grid column, 2 mixture */
+    VIPRS_FAMILY_GRID_BATCHED = 5    /* batched grid kernel on the matrix cores: one launch per 32 active columns, a 1-model
+                                        prologue launch in front of every launch after the first */
+};
+enum viprs_route_field {
+    VIPRS_ROUTE_DENSE_FAMILY = 0, VIPRS_ROUTE_DENSE_MODEL = 1,      /* the generic and tile families take the model kind */
+    VIPRS_ROUTE_RAGGED_FAMILY = 2, VIPRS_ROUTE_RAGGED_MODEL = 3,
+    VIPRS_ROUTE_PROLOGUE = 4,                 /* the launch that zeroes queue heads, skip count and hand-off granules */
+    VIPRS_ROUTE_PROLOGUE_PER_MODEL = 5,       /* ... granules for every active model (grid), not for one */
+    VIPRS_ROUTE_START_EVENT_BY_LAUNCHER = 6,  /* the dominant kernel's start event is recorded adjacent to its launch */
+    VIPRS_ROUTE_WHOLE_SWEEP_EVENTS = 7,       /* an event pair around everything beside the dominant kernel's own pair;
+                                                 0: that pair goes around all kernels of the call and stands for both */
+    VIPRS_ROUTE_DENSE_BRACKETED = 8,          /* the dominant kernel's pair is recorded at all */
+    VIPRS_ROUTE_COUNT = 9
+};
+int viprs_sweep_route(int float_dtype, int model_kind, int width, int ld_dtype, int dense, int ragged, int band_ok,
+                      int grid_mfma, int f64_row_by_row, int* route);
 
 /* ---- LD product: Y = R B over EVERY block of a plan -------------------------------------------------------------------
  * What the reference computes with `ld.dot(B)`: the pseudo-validation metrics against a validation LD panel

@@ -83,6 +83,30 @@ def test_banded_next_to_dense_blocks(gpu, low_memory):
     H.assert_state_equal(H.run_hip(ld, inp, st0, sweeps=2), H.run_oracle(ld, inp, st0, sweeps=2))
 
 
+def dense_beside_banded(sizes, m_band, w, low_memory, seed=8):
+    """One LD of dense blocks `sizes` followed by one windowed component of `m_band` SNPs with window `w` on each side."""
+    dense = syn.make_ld(sizes, low_memory=low_memory, seed=3)
+    band = banded_ld(m_band, w, w, low_memory, np.float32, seed=seed)
+    m0 = dense.m
+    lb = np.concatenate([dense.ld_left_bound, band.ld_left_bound + m0]).astype(np.int32)
+    ip = np.concatenate([dense.ld_indptr, band.ld_indptr[1:] + dense.ld_indptr[-1]]).astype(np.int64)
+    data = np.concatenate([dense.ld_data, band.ld_data])
+    return syn.SyntheticLD(lb, ip, data, np.array([0, m0 + m_band]), np.zeros(1), bool(low_memory), 1.0)
+
+
+@pytest.mark.parametrize("low_memory", [False, True])
+def test_wide_mixture_on_dense_and_windowed_blocks(gpu, low_memory):
+    """K = 9: the wide panel chain on the dense block, the prologue launch in front of it and the generic kernel on the
+    windowed component, in one sweep."""
+    from tests.test_gpu_models import _run_mix
+    from tests.test_oracle_vs_ref import _mixture_inputs
+    from viprs_amd.vi import e_step_hip as S
+    ld = dense_beside_banded([90], 300, 20, low_memory)
+    ss, inp = _inputs(ld.m, seed=16)
+    mix, st0 = _mixture_inputs(ld, ss, 9)
+    H.assert_state_equal(_run_mix(S, ld, inp, mix, st0, 2), _run_mix(O, ld, inp, mix, st0, 2))
+
+
 @pytest.mark.parametrize("low_memory", [False, True])
 def test_banded_grid_models(gpu, low_memory):
     from viprs_amd.vi import e_step_hip as S

@@ -557,7 +557,7 @@ def test_nonfinite_inputs_mixture_and_grid(gpu, model, low_memory, monkeypatch):
 
 
 def test_kernel_time_does_not_depend_on_the_queue_depth(gpu):
-    """The HIP events that time a sweep bracket the kernel launch itself (`record_start_event`, adjacent to
+    """The HIP events that time a sweep bracket the kernel launch itself (`SweepTiming::launcher_start`, adjacent to
     hipLaunchKernel): a sweep submitted into an EMPTY stream -- where the start event is reached at once and anything the
     host does before the launch would count as kernel time -- reports the same kernel time as sweeps submitted back to back.
     (Round 5's driver run showed a 1.9 ms 'sweep' among ten of 0.38: host time inside the bracket; profiles/r06_stall.md.)"""
@@ -589,6 +589,57 @@ def test_kernel_time_does_not_depend_on_the_queue_depth(gpu):
     assert host.shape == (40,) and (host >= 0).all() and np.median(host) < 0.1, host
     slow = np.array(empty) > 1.5 * np.median(empty)
     assert (host[slow] > 0.1).all(), (np.array(empty)[slow], host[slow])      # every outlier is explained by its host stamp
+    plan.close()
+
+
+def test_timing_record_follows_the_route_of_each_sweep(gpu):
+    """The timing record of a sweep holds what THAT sweep bracketed.  One dense block beside one windowed component, fp32
+    spike-and-slab: the dense bracket lies inside the whole sweep's; a sweep over the windowed component only brackets no
+    dense kernel and reports 0 for which = 1 and which = 2 (not the stamps an earlier sweep left in the ring slot); a mixture
+    sweep has one bracket, which stands for both.  The state is `==` the oracle's after the same sweeps over the same blocks."""
+    from tests.test_band import _inputs, dense_beside_banded
+    from tests.test_oracle_vs_ref import _mixture_inputs
+    from viprs_amd import _lib as L
+    from viprs_amd.plan import DeviceState, LDPlan
+    ld = dense_beside_banded([90], 300, 20, False)
+    ss, inp = _inputs(ld.m, seed=21)
+    plan = LDPlan(ld.ld_left_bound, ld.ld_indptr, ld.ld_data, False)
+    assert (plan.info(L.INFO_N_DENSE), plan.info(L.INFO_N_RAGGED)) == (1, 1)
+    st = DeviceState(plan, "float32", "spike_slab")
+    for k in ("std_beta", "u_logs", "sqrt_half_var_tau", "mu_mult") + H.STATE:
+        st.upload(k, getattr(inp, k))
+    plan.timing_reset()
+    st.e_step(ld.dq_scale)
+    whole, dense, host = (plan.timing_history(which=w) for w in (0, 1, 2))
+    assert len(whole) == len(dense) == len(host) == 1
+    assert whole[0] >= dense[0] > 0 and host[0] >= 0, (whole, dense, host)
+    starts, _ = plan.blocks()
+    plan.timing_reset()
+    plan.set_active_blocks(starts[:-1] >= 90)             # the windowed component only
+    st.e_step(ld.dq_scale)
+    assert plan.timing_history(which=1) == [0.0] and plan.timing_history(which=2) == [0.0]
+    assert plan.timing_history(which=0)[0] > 0
+    plan.set_active_blocks(None)
+    st.e_step(ld.dq_scale)
+    for w in (0, 1, 2):
+        t = np.array(plan.timing_history(which=w))
+        assert t.shape == (2,) and np.isfinite(t).all() and (t >= 0).all(), (w, t)
+    # the oracle: LD blocks are independent, so the dense block keeps its state through the second sweep
+    ref1 = H.run_oracle(ld, inp, inp.state_copy(), sweeps=1)
+    ref2 = H.run_oracle(ld, inp, ref1, sweeps=1)
+    for k in H.STATE:
+        ref2[k][:90] = ref1[k][:90]
+    H.assert_state_equal({k: st.download(k) for k in H.STATE}, H.run_oracle(ld, inp, ref2, sweeps=1))
+    # mixture: only one bracket exists on that route
+    mix, st0 = _mixture_inputs(ld, ss, 4)
+    sm = DeviceState(plan, "float32", "mixture", 4)
+    sm.upload("std_beta", inp.std_beta)
+    for k, v in (("log_null_pi", mix["log_null_pi"]), ("u_logs", mix["u_logs"]), ("sqrt_half_var_tau", mix["shvt"]),
+                 ("mu_mult", mix["mu_mult"])) + tuple(st0.items()):
+        sm.upload(k, v)
+    plan.timing_reset()
+    sm.e_step(ld.dq_scale)
+    assert plan.timing_history(which=0) == plan.timing_history(which=1) and plan.timing_history(which=0)[0] > 0
     plan.close()
 
 

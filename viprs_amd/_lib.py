@@ -23,6 +23,10 @@ MODEL_SPIKE_SLAB, MODEL_MIXTURE, MODEL_GRID = 0, 1, 2
 (INFO_M, INFO_NNZ, INFO_N_BLOCKS, INFO_N_DENSE, INFO_N_RAGGED, INFO_MAX_BLOCK, INFO_LD_BYTES_DEVICE,
  INFO_LD_ELEM_SIZE, INFO_DEVICE, INFO_LOW_MEMORY, INFO_N_CU, INFO_UPPER_MIRRORED) = range(12)
 
+(FAMILY_NONE, FAMILY_GENERIC, FAMILY_TILE_F64, FAMILY_PANEL, FAMILY_BAND, FAMILY_GRID_BATCHED) = range(6)
+ROUTE_FIELDS = ("dense_family", "dense_model", "ragged_family", "ragged_model", "prologue", "prologue_per_model",
+                "start_event_by_launcher", "whole_sweep_events", "dense_bracketed")
+
 OK, EINVAL, ELAYOUT, EDEVICE, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 N_SUMS = 11
 COMM_ID_BYTES = 128
@@ -121,6 +125,7 @@ _PROTOS = {
     "viprs_plan_last_math_modes": (_i, [_vp, ctypes.POINTER(_i)]),
     "viprs_plan_timing_reset": (_i, [_vp]),
     "viprs_plan_timing_history": (_i, [_vp, _i, ctypes.POINTER(_d), _i, ctypes.POINTER(_i)]),
+    "viprs_sweep_route": (_i, [_i] * 9 + [ctypes.POINTER(_i)]),
     "viprs_plan_dot": (_i, [_vp, _i, _i, _vp, _vp, _d, _i]),
     "viprs_state_dot": (_i, [_vp, _i, _d, _i, _vp]),
     "viprs_plan_last_dot_ms": (_i, [_vp, ctypes.POINTER(_d)]),
@@ -178,3 +183,11 @@ def device_count():
     n = _i(0)
     rc = lib.viprs_device_count(ctypes.byref(n))
     return n.value if rc == OK else 0
+
+
+def sweep_route(float_dtype, model_kind, width, ld_dtype, dense, ragged, band_ok=True, grid_mfma=False, f64_row_by_row=False):
+    """The route of a sweep (`viprs_sweep_route`, include/viprs_hip.h) as a dict over ROUTE_FIELDS; needs no GPU."""
+    out = (_i * len(ROUTE_FIELDS))()
+    check(lib.viprs_sweep_route(float_dtype, model_kind, width, ld_dtype, int(dense), int(ragged), int(band_ok),
+                                int(grid_mfma), int(f64_row_by_row), out))
+    return dict(zip(ROUTE_FIELDS, out))

@@ -2,6 +2,8 @@
 // serves which blocks of a plan, on which streams -- plus the per-sweep timing hooks.
 #include "internal.h"
 
+#include <type_traits>
+
 using namespace viprs;
 
 namespace {
@@ -22,6 +24,20 @@ hipError_t clear_stale_skip_count(viprs_plan* P) {
     if (!P->skip_count_in_place) return hipSuccess;
     P->skip_count_in_place = false;
     return hipMemsetAsync(P->d_skipped.p, 0, sizeof(unsigned long long), P->stream);
+}
+
+// The prologue launch of a sweep; its kernels count in place.  (Grid launches: one granule set per active model.)
+int sweep_prologue(viprs_plan* P, int n_models) {
+    P->skip_count_in_place = true;
+    const int64_t ng = P->n_granule_rows * kPanel * std::max(1, n_models);
+    if (P->d_granules.n < (size_t)ng) {
+        HIP_TRY(hipStreamSynchronize(P->stream));
+        HIP_TRY(P->d_granules.alloc((size_t)ng));
+    }
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ng + 255) / 256, 1024));
+    sweep_prologue_kernel<<<grid, 256, 0, P->stream>>>(P->d_counters.p, kPlanCounters, P->d_skipped.p, P->d_granules.p, ng);
+    HIP_TRY(hipGetLastError());
+    return VIPRS_OK;
 }
 
 template <typename T>
@@ -57,208 +73,127 @@ EStepArgs<T> make_args(viprs_state* S, double dq) {
     return A;
 }
 
+// One launcher instantiation per LD element type: `f` is called with a value of the type `ld_dtype` names.  The list `Us` is
+// explicit at every call site: the launchers are explicitly instantiated per translation unit for exactly those types, and a
+// dispatch over all six would ask the linker for instantiations that do not exist.
+template <typename U> constexpr int ld_code();
+template <> constexpr int ld_code<int8_t>() { return VIPRS_LD_I8; }
+template <> constexpr int ld_code<int16_t>() { return VIPRS_LD_I16; }
+template <> constexpr int ld_code<int32_t>() { return VIPRS_LD_I32; }
+template <> constexpr int ld_code<int64_t>() { return VIPRS_LD_I64; }
+template <> constexpr int ld_code<float>() { return VIPRS_LD_F32; }
+template <> constexpr int ld_code<double>() { return VIPRS_LD_F64; }
+
+template <typename... Us, typename F>
+int for_ld_type(int ld_dtype, const char* otherwise, F&& f) {
+    int rc = VIPRS_OK;
+    const bool found = ((ld_dtype == ld_code<Us>() && ((rc = f(Us{})), true)) || ...);
+    return found ? rc : fail(VIPRS_EINVAL, otherwise);
+}
+
+// the batched grid kernel, matrix-core path: chunks of 32 models, each LD row read once per chunk
+template <typename U>
+int launch_grid_chunks(viprs_state* S, const EStepArgs<float>& A) {
+    viprs_plan* P = S->plan;
+    const int64_t lists_per_chunk = (int64_t)S->n_groups * kGroupListStride;
+    for (int off = 0; off < A.n_active; off += kGridModels) {
+        EStepArgs<float> Ac = A;
+        Ac.active = A.active + off;
+        Ac.n_active = std::min(kGridModels, A.n_active - off);
+        if (A.group_cols) Ac.group_lists = S->d_group_lists.p + (off / kGridModels) * lists_per_chunk;
+        int rc = off > 0 ? sweep_prologue(P, 1) : VIPRS_OK;
+        if (rc == VIPRS_OK) rc = launch_grid_mfma<U>(P, Ac);
+        if (rc != VIPRS_OK) return rc;
+    }
+    return VIPRS_OK;
+}
+
+// the launcher of one family of a route over one block list
 template <typename T>
-int launch_generic_u(viprs_plan* P, const EStepArgs<T>& A, int model, bool dense) {
-    switch (P->ld_dtype) {
-        case VIPRS_LD_I8: return launch_generic<T, int8_t>(P, A, model, dense);
-        case VIPRS_LD_I16: return launch_generic<T, int16_t>(P, A, model, dense);
-        case VIPRS_LD_I32: return launch_generic<T, int32_t>(P, A, model, dense);
-        case VIPRS_LD_I64: return launch_generic<T, int64_t>(P, A, model, dense);
-        case VIPRS_LD_F32: return launch_generic<T, float>(P, A, model, dense);
-        case VIPRS_LD_F64: return launch_generic<T, double>(P, A, model, dense);
-        default: return fail(VIPRS_EINVAL, "bad LD dtype");
+int launch_family(viprs_state* S, const EStepArgs<T>& A, int family, int model, bool dense) {
+    viprs_plan* P = S->plan;
+    if (family == kFamNone) return VIPRS_OK;
+    if (family == kFamGeneric)
+        return for_ld_type<int8_t, int16_t, int32_t, int64_t, float, double>(P->ld_dtype, "bad LD dtype", [&](auto u) {
+            return launch_generic<T, decltype(u)>(P, A, model, dense); });
+    if constexpr (std::is_same<T, double>::value) {
+        if (family == kFamTileF64)
+            return for_ld_type<int8_t, int16_t, int32_t, int64_t, float, double>(P->ld_dtype, "bad LD dtype", [&](auto u) {
+                return launch_tile_f64<decltype(u)>(P, A, model, dense); });
+    } else {
+        // (kPanelGridColumn: ONE launch over (block, model) work items, select_model offsets the columns in-kernel)
+        if (family == kFamPanel)
+            return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
+                return launch_panel<decltype(u)>(P, A, model); });
+        if (family == kFamBand)
+            return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kBandLdTypeError, [&](auto u) {
+                return launch_band<decltype(u)>(P, A, model); });
+        if (family == kFamGridBatched)
+            return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
+                return launch_grid_chunks<decltype(u)>(S, A); });
     }
+    return fail(VIPRS_EINVAL, "kernel family without an instantiation for the state precision");
 }
 
-int launch_tile_f64_u(viprs_plan* P, const EStepArgs<double>& A, int model, bool dense) {
-    if (getenv("VIPRS_F64_ROW_BY_ROW")) return launch_generic_u<double>(P, A, model, dense);      // experiments / A-B
-    switch (P->ld_dtype) {
-        case VIPRS_LD_I8: return launch_tile_f64<int8_t>(P, A, model, dense);
-        case VIPRS_LD_I16: return launch_tile_f64<int16_t>(P, A, model, dense);
-        case VIPRS_LD_I32: return launch_tile_f64<int32_t>(P, A, model, dense);
-        case VIPRS_LD_I64: return launch_tile_f64<int64_t>(P, A, model, dense);
-        case VIPRS_LD_F32: return launch_tile_f64<float>(P, A, model, dense);
-        case VIPRS_LD_F64: return launch_tile_f64<double>(P, A, model, dense);
-        default: return fail(VIPRS_EINVAL, "bad LD dtype");
+// the launchers of a route, in stream order, between the events of the timing record
+template <typename T>
+int launch_route(viprs_state* S, const SweepRoute& r, double dq, const int32_t* d_active, int n_active) {
+    viprs_plan* P = S->plan;
+    EStepArgs<T> A = make_args<T>(S, dq);
+    A.active = d_active;
+    A.n_active = n_active;
+    if (S->model_kind == VIPRS_MODEL_GRID && !S->group_cols_h.empty()) {     // (group_mask_prepare: fp32 state, dense blocks only)
+        A.blk_group = S->d_blk_group.p;
+        A.group_cols = S->d_group_cols.p;
     }
+    int rc = launch_family<T>(S, A, r.dense_family, r.dense_model, true);
+    if (rc != VIPRS_OK) return rc;
+    rc = P->timing.dense_done();
+    if (rc != VIPRS_OK) return rc;
+    return launch_family<T>(S, A, r.ragged_family, r.ragged_model, false);
 }
 
-int launch_panel_u(viprs_plan* P, const EStepArgs<float>& A, int model) {
-    switch (P->ld_dtype) {
-        case VIPRS_LD_F32: return launch_panel<float>(P, A, model);
-        case VIPRS_LD_I8: return launch_panel<int8_t>(P, A, model);
-        case VIPRS_LD_I16: return launch_panel<int16_t>(P, A, model);
-        default: return fail(VIPRS_EINVAL, "dense schedule with unsupported LD dtype");
-    }
-}
-
-bool use_band(const viprs_plan* P) {
+// Environment switches are read per call (tests flip them between sweeps).
+bool band_ok(const viprs_plan* P) {
     const char* f = getenv("VIPRS_BAND");
-    if ((f && !atoi(f)) || P->ragged_h.empty()) return false;
+    if (f && !atoi(f)) return false;
     if (P->ld_dtype != VIPRS_LD_F32 && P->ld_dtype != VIPRS_LD_I8 && P->ld_dtype != VIPRS_LD_I16) return false;
     return band_ring_panels(P) <= kBandMaxRingPanels;
 }
 
-int launch_band_u(viprs_plan* P, const EStepArgs<float>& A, int model) {
-    switch (P->ld_dtype) {
-        case VIPRS_LD_F32: return launch_band<float>(P, A, model);
-        case VIPRS_LD_I8: return launch_band<int8_t>(P, A, model);
-        case VIPRS_LD_I16: return launch_band<int16_t>(P, A, model);
-        default: return fail(VIPRS_EINVAL, "band schedule with unsupported LD dtype");
-    }
-}
-
-int run_spike_slab(viprs_state* S, double dq) {
-    viprs_plan* P = S->plan;
-    HIP_TRY(hipSetDevice(P->device));
-    // two HIP events per sweep when the dense kernels are all there is (the common case): [2] .. [3] then also
-    // stand for the whole sweep; every event record costs stream time
-    const bool dense_only = S->float_dtype == VIPRS_F32 && !P->dense_h.empty() && P->ragged_h.empty();
-    // (dense blocks only: the panel sweep is the only kernel of the call and keeps its own books -- generation-tagged
-    // hand-off granules, queue heads reset and the skip count published by its last workgroup: no prologue launch)
-    if (!dense_only) {
-        const int64_t ng = P->n_granule_rows * kPanel;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ng + 255) / 256, 1024));
-        sweep_prologue_kernel<<<grid, 256, 0, P->stream>>>(P->d_counters.p, kPlanCounters, P->d_skipped.p, P->d_granules.p, ng);
-        HIP_TRY(hipGetLastError());
-        P->skip_count_in_place = true;
-    } else {
-        HIP_TRY(clear_stale_skip_count(P));
-    }
-    P->math_used = 0;
-    hipEvent_t* ev = P->ev.data() + 4 * (P->sweeps % viprs_plan::kRing);
-    P->ev_dense_only[P->sweeps % viprs_plan::kRing] = dense_only;
-    if (!dense_only) HIP_TRY(hipEventRecord(ev[0], P->stream));
-    int rc = VIPRS_OK;
-    if (S->float_dtype == VIPRS_F32) {
-        EStepArgs<float> A = make_args<float>(S, dq);
-        if (!P->dense_h.empty()) {
-            P->pending_start_event = ev[2];              // recorded by the launcher, adjacent to the kernel launch
-            switch (P->ld_dtype) {
-                case VIPRS_LD_F32: rc = launch_panel<float>(P, A, kPanelSpikeSlab); break;
-                case VIPRS_LD_I8: rc = launch_panel<int8_t>(P, A, kPanelSpikeSlab); break;
-                case VIPRS_LD_I16: rc = launch_panel<int16_t>(P, A, kPanelSpikeSlab); break;
-                default: rc = fail(VIPRS_EINVAL, "dense schedule with unsupported LD dtype"); break;
-            }
-            if (rc != VIPRS_OK) { P->pending_start_event = nullptr; return rc; }
-            HIP_TRY(hipEventRecord(ev[3], P->stream));
-            P->host_t1[P->sweeps % viprs_plan::kRing] = host_clock_ms();
-        }
-        if (use_band(P)) rc = launch_band_u(P, A, kBandSpikeSlab);
-        else if (!P->ragged_h.empty()) rc = launch_generic_u<float>(P, A, kGenSpikeSlab, false);
-    } else {
-        // float64 state: the panel kernels specialise float; every block takes the panel-walking kernel of estep_tile.h
-        EStepArgs<double> A = make_args<double>(S, dq);
-        if (!P->dense_h.empty()) { P->host_t0[P->sweeps % viprs_plan::kRing] = host_clock_ms(); HIP_TRY(hipEventRecord(ev[2], P->stream)); }
-        rc = launch_tile_f64_u(P, A, kGenSpikeSlab, true);
-        if (rc == VIPRS_OK && !P->dense_h.empty()) { HIP_TRY(hipEventRecord(ev[3], P->stream)); P->host_t1[P->sweeps % viprs_plan::kRing] = host_clock_ms(); }
-        if (rc == VIPRS_OK) rc = launch_tile_f64_u(P, A, kGenSpikeSlab, false);
-    }
-    if (rc != VIPRS_OK) return rc;
-    if (!dense_only) HIP_TRY(hipEventRecord(ev[1], P->stream));
-    P->sweeps++;
-    return VIPRS_OK;
-}
-
-static int sweep_prologue(viprs_plan* P, int n_models = 1) {
-    P->skip_count_in_place = true;
-    const int64_t ng = P->n_granule_rows * kPanel * std::max(1, n_models);
-    if (P->d_granules.n < (size_t)ng) {                      // grid launches: one granule set per active model
-        HIP_TRY(hipStreamSynchronize(P->stream));
-        HIP_TRY(P->d_granules.alloc((size_t)ng));
-    }
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ng + 255) / 256, 1024));
-    sweep_prologue_kernel<<<grid, 256, 0, P->stream>>>(P->d_counters.p, kPlanCounters, P->d_skipped.p, P->d_granules.p, ng);
-    HIP_TRY(hipGetLastError());
-    return VIPRS_OK;
-}
-
 // One workgroup per LD block: worth it once the blocks can occupy a good part of the chip; with a few
 // blocks the (block, model) work items of the panel kernel spread better.  32-bit element offsets.
-static bool use_grid_mfma(const viprs_plan* P, int width) {
+bool use_grid_mfma(const viprs_plan* P, int width) {
     if ((int64_t)P->m * std::max(1, width) >= (1LL << 31)) return false;
     if (P->grid_mfma >= 0) return P->grid_mfma != 0;
     return (int64_t)P->dense_h.size() * 8 >= (int64_t)P->n_cu * 3;
 }
 
-static int launch_grid_mfma_u(viprs_plan* P, const EStepArgs<float>& A) {
-    switch (P->ld_dtype) {
-        case VIPRS_LD_F32: return launch_grid_mfma<float>(P, A);
-        case VIPRS_LD_I8: return launch_grid_mfma<int8_t>(P, A);
-        case VIPRS_LD_I16: return launch_grid_mfma<int16_t>(P, A);
-        default: return fail(VIPRS_EINVAL, "dense schedule with unsupported LD dtype");
-    }
-}
-
-// mixture / grid.  fp32 state on dense blocks: the panel kernels with the model's policy (the grid
-// runs its independent models one after the other, each on its own column of the (m, G) arrays);
-// everything else (ragged blocks, fp64 state, K > kPanelWideMaxK): the generic kernels.
-int run_generic_model(viprs_state* S, double dq, int model, const int32_t* d_active, int n_active,
-                      const int32_t* h_active) {
+// One sweep of any model: the route (sweep_route.h) says which kernel family serves which block list, whether the prologue
+// launch is needed and which events are recorded; this function executes it.
+int run_sweep(viprs_state* S, double dq, const int32_t* d_active, int n_active) {
+    static_assert(kGenSpikeSlab == VIPRS_MODEL_SPIKE_SLAB && kGenMixture == VIPRS_MODEL_MIXTURE && kGenGrid == VIPRS_MODEL_GRID, "");
     viprs_plan* P = S->plan;
     HIP_TRY(hipSetDevice(P->device));
-    // (the panel sweep keeps its own books, run_spike_slab: no prologue launch when it is the only kernel of the call)
-    const bool panel_only = S->float_dtype == VIPRS_F32 && !P->dense_h.empty() && P->ragged_h.empty() &&
-                            ((model == kGenMixture && S->width <= kPanelWideMaxK) || (model == kGenGrid && !use_grid_mfma(P, S->width)));
-    int rc = panel_only ? VIPRS_OK : sweep_prologue(P, model == kGenGrid ? n_active : 1);
+    const SweepConfig c{S->float_dtype, S->model_kind, S->width, P->ld_dtype, !P->dense_h.empty(), !P->ragged_h.empty(), band_ok(P),
+                        use_grid_mfma(P, S->width), getenv("VIPRS_F64_ROW_BY_ROW") != nullptr};
+    SweepRoute r;
+    std::string err;
+    int rc = sweep_route(c, r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    // begin the sweep: the books of the kernels, then the timing slot
+    if (r.prologue) rc = sweep_prologue(P, r.prologue_per_model ? n_active : 1);
+    else HIP_TRY(clear_stale_skip_count(P));
     if (rc != VIPRS_OK) return rc;
-    if (panel_only) HIP_TRY(clear_stale_skip_count(P));
     P->math_used = 0;
-    hipEvent_t* ev = P->ev.data() + 4 * (P->sweeps % viprs_plan::kRing);
-    P->ev_dense_only[P->sweeps % viprs_plan::kRing] = true;      // [2] .. [3] bracket all kernels of the call
-    {
-        // the panel and batched-grid launchers record the start event themselves, adjacent to their (first) kernel launch
-        const bool panel_ok0 = S->float_dtype == VIPRS_F32 && !P->dense_h.empty() && (model == kGenGrid || S->width <= kPanelWideMaxK);
-        if (panel_ok0) P->pending_start_event = ev[2];
-        else { P->host_t0[P->sweeps % viprs_plan::kRing] = host_clock_ms(); HIP_TRY(hipEventRecord(ev[2], P->stream)); }
-    }
-    if (S->float_dtype == VIPRS_F32) {
-        EStepArgs<float> A = make_args<float>(S, dq);
-        A.active = d_active;
-        A.n_active = n_active;
-        if (model == kGenGrid && !S->group_cols_h.empty()) {     // (group_mask_prepare: dense blocks only)
-            A.blk_group = S->d_blk_group.p;
-            A.group_cols = S->d_group_cols.p;
-        }
-        const int64_t lists_per_chunk = (int64_t)S->n_groups * kGroupListStride;
-        const bool panel_ok = !P->dense_h.empty() && (model == kGenGrid || S->width <= kPanelWideMaxK);
-        if (panel_ok && model == kGenMixture) {
-            rc = launch_panel_u(P, A, S->width <= kPanelMaxK ? kPanelMixture : kPanelMixtureWide);
-        } else if (panel_ok && model == kGenGrid && use_grid_mfma(P, A.width)) {
-            // matrix-core path: chunks of 32 models, each LD row read once per chunk
-            for (int off = 0; off < n_active && rc == VIPRS_OK; off += kGridModels) {
-                EStepArgs<float> Ac = A;
-                Ac.active = d_active + off;
-                Ac.n_active = std::min(kGridModels, n_active - off);
-                if (A.group_cols) Ac.group_lists = S->d_group_lists.p + (off / kGridModels) * lists_per_chunk;
-                if (off > 0) rc = sweep_prologue(P, 1);
-                if (rc == VIPRS_OK) rc = launch_grid_mfma_u(P, Ac);
-            }
-        } else if (panel_ok && model == kGenGrid) {
-            // ONE launch over (block, model) work items (select_model offsets the columns in-kernel)
-            A.granules = P->d_granules.p;
-            rc = launch_panel_u(P, A, kPanelGridColumn);
-        } else {
-            rc = launch_generic_u<float>(P, A, model, true);
-        }
-        if (rc == VIPRS_OK) {
-            if (model == kGenGrid && use_band(P)) rc = launch_band_u(P, A, kBandGridColumn);
-            else if (model == kGenMixture && S->width <= kPanelMaxK && use_band(P)) rc = launch_band_u(P, A, kBandMixture);
-            else rc = launch_generic_u<float>(P, A, model, false);
-        }
-    } else {
-        EStepArgs<double> A = make_args<double>(S, dq);
-        A.active = d_active;
-        A.n_active = n_active;
-        rc = launch_tile_f64_u(P, A, model, true);
-        if (rc == VIPRS_OK) rc = launch_tile_f64_u(P, A, model, false);
-    }
-    if (rc != VIPRS_OK) { P->pending_start_event = nullptr; return rc; }
-    { const int rc2 = record_start_event(P); if (rc2 != VIPRS_OK) return rc2; }      // (never pending here; belt and braces)
-    HIP_TRY(hipEventRecord(ev[3], P->stream));
-    P->host_t1[P->sweeps % viprs_plan::kRing] = host_clock_ms();
-    P->sweeps++;
-    return VIPRS_OK;
+    rc = P->timing.open(r.whole_sweep_events, r.dense_bracketed);
+    if (rc != VIPRS_OK) return rc;
+    if (r.dense_bracketed && r.start_event_by_launcher) P->timing.arm();
+    else if (r.dense_bracketed) { rc = P->timing.start(); if (rc != VIPRS_OK) return rc; }
+    rc = S->float_dtype == VIPRS_F32 ? launch_route<float>(S, r, dq, d_active, n_active)
+                                     : launch_route<double>(S, r, dq, d_active, n_active);
+    if (rc != VIPRS_OK) { P->timing.abandon(); return rc; }
+    return P->timing.close();
 }
 
 // A grid state with SNP groups under a (group, column) mask (viprs_state_set_group_columns): the batched matrix-core kernel
@@ -310,8 +245,7 @@ int viprs_state_e_step(viprs_state* S, double dq_scale, const int32_t* active, i
     if (!S) return fail(VIPRS_EINVAL, "null state");
     int rc;
     switch (S->model_kind) {
-        case VIPRS_MODEL_SPIKE_SLAB: rc = run_spike_slab(S, dq_scale); break;
-        case VIPRS_MODEL_MIXTURE: rc = run_generic_model(S, dq_scale, kGenMixture, nullptr, 0, nullptr); break;
+        case VIPRS_MODEL_SPIKE_SLAB: case VIPRS_MODEL_MIXTURE: rc = run_sweep(S, dq_scale, nullptr, 0); break;
         case VIPRS_MODEL_GRID: {
             std::vector<int32_t> all;
             if (!active) {                                    // default: every model is active
@@ -332,7 +266,7 @@ int viprs_state_e_step(viprs_state* S, double dq_scale, const int32_t* active, i
             HIP_TRY(hipMemcpyAsync(S->d_active.p, active, sizeof(int32_t) * (size_t)n_active, hipMemcpyHostToDevice,
                                    S->plan->stream));
             HIP_TRY(hipStreamSynchronize(S->plan->stream));   // `active` may be a temporary
-            rc = run_generic_model(S, dq_scale, kGenGrid, S->d_active.p, n_active, active);
+            rc = run_sweep(S, dq_scale, S->d_active.p, n_active);
             break;
         }
         default: return fail(VIPRS_EINVAL, "bad model kind");
@@ -340,6 +274,36 @@ int viprs_state_e_step(viprs_state* S, double dq_scale, const int32_t* active, i
     if (rc != VIPRS_OK) return rc;
     if (sync) HIP_TRY(hipStreamSynchronize(S->plan->stream));
     return VIPRS_OK;
+}
+
+// The one-shot calls: the plan's scratch state of that precision, model and width takes the caller's buffers (`host`: one
+// pointer per viprs_field, in the order of the enum), is swept once and hands the five state fields back.
+static int one_shot(viprs_plan* P, int float_dtype, int model_kind, int width, const void* const (&host)[VIPRS_FIELD_COUNT],
+                    double dq, const int32_t* active, int n_active) {
+    viprs_state* S = P->scratch;
+    if (!S || S->float_dtype != float_dtype || S->model_kind != model_kind || S->width != width) {
+        delete P->scratch;
+        P->scratch = nullptr;
+        int rc = viprs_state_create(&P->scratch, P, float_dtype, model_kind, width);
+        if (rc != VIPRS_OK) return rc;
+        S = P->scratch;
+    }
+    const size_t fs = float_size(S->float_dtype);
+    HIP_TRY(hipSetDevice(P->device));
+    // (a field the model does not have -- log_null_pi outside the mixture -- has no bytes)
+    for (int f : {VIPRS_FIELD_STD_BETA, VIPRS_FIELD_LOG_NULL_PI, VIPRS_FIELD_U_LOGS, VIPRS_FIELD_SQRT_HALF_VAR_TAU, VIPRS_FIELD_MU_MULT,
+                  VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF}) {
+        const size_t bytes = S->field_elems(f) * fs;
+        if (bytes == 0) continue;
+        if (!host[f]) return fail(VIPRS_EINVAL, "null buffer");
+        HIP_TRY(hipMemcpyAsync(S->f[f].p, host[f], bytes, hipMemcpyHostToDevice, P->stream));
+    }
+    int rc = viprs_state_e_step(S, dq, active, n_active, 0);
+    if (rc != VIPRS_OK) return rc;
+    for (int f : {VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF})
+        HIP_TRY(hipMemcpyAsync(const_cast<void*>(host[f]), S->f[f].p, S->field_elems(f) * fs, hipMemcpyDeviceToHost, P->stream));
+    HIP_TRY(hipStreamSynchronize(P->stream));
+    return check_device_error(P);                      // a timed-out team hand-off must not return silently
 }
 
 int viprs_e_step(viprs_plan* P, int float_dtype, const void* std_beta, void* var_gamma, void* var_mu, void* eta,
@@ -350,63 +314,8 @@ int viprs_e_step(viprs_plan* P, int float_dtype, const void* std_beta, void* var
     if ((low_memory != 0) != (P->low_memory != 0))
         return fail(VIPRS_EINVAL, "low_memory differs from the value the plan was created with");
     if (P->m == 0) return VIPRS_OK;
-    if (!P->scratch || P->scratch->float_dtype != float_dtype || P->scratch->model_kind != VIPRS_MODEL_SPIKE_SLAB) {
-        delete P->scratch;
-        P->scratch = nullptr;
-        int rc = viprs_state_create(&P->scratch, P, float_dtype, VIPRS_MODEL_SPIKE_SLAB, 1);
-        if (rc != VIPRS_OK) return rc;
-    }
-    viprs_state* S = P->scratch;
-    const size_t bytes = (size_t)P->m * float_size(float_dtype);
-    const void* ins[] = {std_beta, u_logs, shvt, mu_mult, var_gamma, var_mu, eta, q, eta_diff};
-    const int in_fields[] = {VIPRS_FIELD_STD_BETA, VIPRS_FIELD_U_LOGS, VIPRS_FIELD_SQRT_HALF_VAR_TAU, VIPRS_FIELD_MU_MULT,
-                             VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF};
-    HIP_TRY(hipSetDevice(P->device));
-    for (int i = 0; i < 9; ++i) {
-        if (!ins[i]) return fail(VIPRS_EINVAL, "null buffer");
-        HIP_TRY(hipMemcpyAsync(S->f[in_fields[i]].p, ins[i], bytes, hipMemcpyHostToDevice, P->stream));
-    }
-    int rc = run_spike_slab(S, dq_scale);
-    if (rc != VIPRS_OK) return rc;
-    void* outs[] = {var_gamma, var_mu, eta, q, eta_diff};
-    const int out_fields[] = {VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF};
-    for (int i = 0; i < 5; ++i)
-        HIP_TRY(hipMemcpyAsync(outs[i], S->f[out_fields[i]].p, bytes, hipMemcpyDeviceToHost, P->stream));
-    HIP_TRY(hipStreamSynchronize(P->stream));
-    return check_device_error(P);
-}
-
-static int scratch_state(viprs_plan* P, int float_dtype, int model_kind, int width, viprs_state** out) {
-    viprs_state* S = P->scratch;
-    if (!S || S->float_dtype != float_dtype || S->model_kind != model_kind || S->width != width) {
-        delete P->scratch;
-        P->scratch = nullptr;
-        int rc = viprs_state_create(&P->scratch, P, float_dtype, model_kind, width);
-        if (rc != VIPRS_OK) return rc;
-    }
-    *out = P->scratch;
-    return VIPRS_OK;
-}
-
-static int one_shot(viprs_state* S, const void* const* ins, const int* in_fields, int n_in, void* const* outs,
-                    const int* out_fields, int n_out, double dq, const int32_t* active, int n_active) {
-    viprs_plan* P = S->plan;
-    const size_t fs = float_size(S->float_dtype);
-    HIP_TRY(hipSetDevice(P->device));
-    for (int i = 0; i < n_in; ++i) {
-        const size_t bytes = S->field_elems(in_fields[i]) * fs;
-        if (bytes == 0) continue;
-        if (!ins[i]) return fail(VIPRS_EINVAL, "null buffer");
-        HIP_TRY(hipMemcpyAsync(S->f[in_fields[i]].p, ins[i], bytes, hipMemcpyHostToDevice, P->stream));
-    }
-    int rc = viprs_state_e_step(S, dq, active, n_active, 0);
-    if (rc != VIPRS_OK) return rc;
-    for (int i = 0; i < n_out; ++i) {
-        const size_t bytes = S->field_elems(out_fields[i]) * fs;
-        HIP_TRY(hipMemcpyAsync(outs[i], S->f[out_fields[i]].p, bytes, hipMemcpyDeviceToHost, P->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(P->stream));
-    return check_device_error(P);                      // a timed-out team hand-off must not return silently
+    const void* const host[] = {std_beta, u_logs, shvt, mu_mult, nullptr, var_gamma, var_mu, eta, q, eta_diff};
+    return one_shot(P, float_dtype, VIPRS_MODEL_SPIKE_SLAB, 1, host, dq_scale, nullptr, 0);
 }
 
 int viprs_e_step_mixture(viprs_plan* P, int float_dtype, int K, const void* std_beta, void* var_gamma, void* var_mu,
@@ -418,16 +327,8 @@ int viprs_e_step_mixture(viprs_plan* P, int float_dtype, int K, const void* std_
         return fail(VIPRS_EINVAL, "low_memory differs from the value the plan was created with");
     if (K < 1) return fail(VIPRS_EINVAL, "K must be >= 1");
     if (P->m == 0) return VIPRS_OK;
-    viprs_state* S = nullptr;
-    int rc = scratch_state(P, float_dtype, VIPRS_MODEL_MIXTURE, K, &S);
-    if (rc != VIPRS_OK) return rc;
-    const void* ins[] = {std_beta, log_null_pi, u_logs, shvt, mu_mult, var_gamma, var_mu, eta, q, eta_diff};
-    const int in_fields[] = {VIPRS_FIELD_STD_BETA, VIPRS_FIELD_LOG_NULL_PI, VIPRS_FIELD_U_LOGS,
-                             VIPRS_FIELD_SQRT_HALF_VAR_TAU, VIPRS_FIELD_MU_MULT, VIPRS_FIELD_VAR_GAMMA,
-                             VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF};
-    void* outs[] = {var_gamma, var_mu, eta, q, eta_diff};
-    const int out_fields[] = {VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF};
-    return one_shot(S, ins, in_fields, 10, outs, out_fields, 5, dq_scale, nullptr, 0);
+    const void* const host[] = {std_beta, u_logs, shvt, mu_mult, log_null_pi, var_gamma, var_mu, eta, q, eta_diff};
+    return one_shot(P, float_dtype, VIPRS_MODEL_MIXTURE, K, host, dq_scale, nullptr, 0);
 }
 
 int viprs_e_step_grid(viprs_plan* P, int float_dtype, int G, const void* std_beta, void* var_gamma, void* var_mu,
@@ -441,62 +342,52 @@ int viprs_e_step_grid(viprs_plan* P, int float_dtype, int G, const void* std_bet
     if (G < 1) return fail(VIPRS_EINVAL, "G must be >= 1");
     if (n_active < 0 || (n_active > 0 && !active_model_idx)) return fail(VIPRS_EINVAL, "bad active_model_idx");
     if (P->m == 0 || n_active == 0) return VIPRS_OK;
-    viprs_state* S = nullptr;
-    int rc = scratch_state(P, float_dtype, VIPRS_MODEL_GRID, G, &S);
-    if (rc != VIPRS_OK) return rc;
-    const void* ins[] = {std_beta, u_logs, half_var_tau, mu_mult, var_gamma, var_mu, eta, q, eta_diff};
-    const int in_fields[] = {VIPRS_FIELD_STD_BETA, VIPRS_FIELD_U_LOGS, VIPRS_FIELD_SQRT_HALF_VAR_TAU, VIPRS_FIELD_MU_MULT,
-                             VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF};
-    void* outs[] = {var_gamma, var_mu, eta, q, eta_diff};
-    const int out_fields[] = {VIPRS_FIELD_VAR_GAMMA, VIPRS_FIELD_VAR_MU, VIPRS_FIELD_ETA, VIPRS_FIELD_Q, VIPRS_FIELD_ETA_DIFF};
-    return one_shot(S, ins, in_fields, 9, outs, out_fields, 5, dq_scale, active_model_idx, n_active);
-}
-
-static int sweep_ms(viprs_plan* P, int64_t sweep, int which, double* ms) {
-    hipEvent_t* ev = P->ev.data() + 4 * (sweep % viprs_plan::kRing);
-    float t = 0.f;
-    if (which == 2) {           // host time between the record of the dominant kernel's start event and the record of its end event
-        const double d = P->host_t1[sweep % viprs_plan::kRing] - P->host_t0[sweep % viprs_plan::kRing];
-        *ms = d > 0.0 ? d : 0.0;
-        return VIPRS_OK;
-    }
-    if (which == 1 || P->ev_dense_only[sweep % viprs_plan::kRing]) {
-        if (which == 1 && P->dense_h.empty() && !P->ev_dense_only[sweep % viprs_plan::kRing]) { *ms = 0.0; return VIPRS_OK; }
-        HIP_TRY(hipEventSynchronize(ev[3]));
-        HIP_TRY(hipEventElapsedTime(&t, ev[2], ev[3]));
-    } else {
-        HIP_TRY(hipEventSynchronize(ev[1]));
-        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-    }
-    *ms = t;
-    return VIPRS_OK;
+    const void* const host[] = {std_beta, u_logs, half_var_tau, mu_mult, nullptr, var_gamma, var_mu, eta, q, eta_diff};
+    return one_shot(P, float_dtype, VIPRS_MODEL_GRID, G, host, dq_scale, active_model_idx, n_active);
 }
 
 int viprs_plan_last_kernel_ms(viprs_plan* P, int which, double* ms) {
     if (!P || !ms) return fail(VIPRS_EINVAL, "null argument");
-    if (P->sweeps == 0) return fail(VIPRS_EINVAL, "no timed sweep yet");
+    if (P->timing.sweeps == 0) return fail(VIPRS_EINVAL, "no timed sweep yet");
     HIP_TRY(hipSetDevice(P->device));
-    return sweep_ms(P, P->sweeps - 1, which, ms);
+    return P->timing.elapsed(P->timing.sweeps - 1, which, ms);
 }
 
 int viprs_plan_timing_reset(viprs_plan* P) {
     if (!P) return fail(VIPRS_EINVAL, "null plan");
     HIP_TRY(hipSetDevice(P->device));
     HIP_TRY(hipStreamSynchronize(P->stream));
-    P->sweeps = 0;
+    P->timing.reset();
     return VIPRS_OK;
 }
 
 int viprs_plan_timing_history(viprs_plan* P, int which, double* ms, int capacity, int* n) {
     if (!P || !ms || !n) return fail(VIPRS_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(P->device));
-    const int64_t have = std::min<int64_t>(P->sweeps, viprs_plan::kRing);
+    const int64_t have = std::min<int64_t>(P->timing.sweeps, SweepTiming::kRing);
     const int count = (int)std::min<int64_t>(have, capacity);
     for (int i = 0; i < count; ++i) {
-        int rc = sweep_ms(P, P->sweeps - count + i, which, &ms[i]);
+        int rc = P->timing.elapsed(P->timing.sweeps - count + i, which, &ms[i]);
         if (rc != VIPRS_OK) return rc;
     }
     *n = count;
+    return VIPRS_OK;
+}
+
+int viprs_sweep_route(int float_dtype, int model_kind, int width, int ld_dtype, int dense, int ragged, int band_ok,
+                      int grid_mfma, int f64_row_by_row, int* route) {
+    if (!route) return fail(VIPRS_EINVAL, "null argument");
+    if ((float_dtype != VIPRS_F32 && float_dtype != VIPRS_F64) || model_kind < kGenSpikeSlab || model_kind > kGenGrid || width < 1)
+        return fail(VIPRS_EINVAL, "bad state precision, model kind or width");
+    const SweepConfig c{float_dtype, model_kind, width, ld_dtype, dense != 0, ragged != 0, band_ok != 0, grid_mfma != 0,
+                        f64_row_by_row != 0};
+    SweepRoute r;
+    std::string err;
+    const int rc = sweep_route(c, r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    const int out[VIPRS_ROUTE_COUNT] = {r.dense_family, r.dense_model, r.ragged_family, r.ragged_model, r.prologue,
+                                        r.prologue_per_model, r.start_event_by_launcher, r.whole_sweep_events, r.dense_bracketed};
+    std::copy(out, out + VIPRS_ROUTE_COUNT, route);
     return VIPRS_OK;
 }
 

@@ -131,7 +131,6 @@ namespace viprs { void team_launch_forget(const viprs_plan* P); }
 viprs_plan::~viprs_plan() {
     viprs::team_launch_forget(this);           // (a later plan may get this address or this stream handle)
     delete scratch;
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
     if (side_stream) (void)hipStreamDestroy(side_stream);
@@ -196,8 +195,8 @@ static int plan_create_impl(viprs_plan** out, int64_t m, const int32_t* lb, cons
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     P->n_cu = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&P->stream, hipStreamNonBlocking));
-    P->ev.assign(4 * viprs_plan::kRing, nullptr);
-    for (auto& e : P->ev) HIP_TRY(hipEventCreate(&e));
+    rc = P->timing.create(P->stream);
+    if (rc != VIPRS_OK) return rc;
 
     // ---- schedule: dense blocks -> panel kernels, everything else -> generic kernel ----------
     // The panel kernels specialise T = float and U in {f32, i8, i16}; other LD dtypes run generic.
@@ -383,9 +382,6 @@ static int plan_create_impl(viprs_plan** out, int64_t m, const int32_t* lb, cons
     P->dense_all_h = P->dense_h;
     P->ragged_all_h = P->ragged_h;
     std::copy(P->class_begin, P->class_begin + 4, P->class_begin_all);
-    P->max_dense_all = P->max_dense;
-    P->max_ragged_all = P->max_ragged;
-    P->m_active = m;
     if (!P->dense_h.empty()) {
         HIP_TRY(P->d_dense_all.alloc(P->dense_h.size()));
         HIP_TRY(hipMemcpy(P->d_dense_all.p, P->dense_h.data(), sizeof(BlockDesc) * P->dense_h.size(), hipMemcpyHostToDevice));
@@ -428,14 +424,6 @@ std::map<int, const viprs_plan*> g_gate_plan;  // ... and the plan whose stream 
 }  // namespace
 double host_clock_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-int record_start_event(viprs_plan* P) {
-    if (P->pending_start_event) {
-        P->host_t0[P->sweeps % viprs_plan::kRing] = host_clock_ms();
-        HIP_TRY(hipEventRecord(P->pending_start_event, P->stream));
-        P->pending_start_event = nullptr;
-    }
-    return VIPRS_OK;
 }
 int team_launch_gate(viprs_plan* P) {
     std::lock_guard<std::mutex> lock(g_gate_mutex);
@@ -656,7 +644,6 @@ int viprs_plan_set_active_blocks(viprs_plan* P, const uint8_t* active, int64_t n
     P->dense_h.clear();
     P->ragged_h.clear();
     P->max_dense = P->max_ragged = 0;
-    P->m_active = 0;
     int cb[4] = {0, 0, 0, 0};
     for (size_t i = 0; i < P->dense_all_h.size(); ++i) {
         const BlockDesc& d = P->dense_all_h[i];
@@ -665,14 +652,12 @@ int viprs_plan_set_active_blocks(viprs_plan* P, const uint8_t* active, int64_t n
         for (int c = cls + 1; c < 4; ++c) ++cb[c];
         P->dense_h.push_back(d);                          // (the full list is in descending order of size: so is this one)
         P->max_dense = std::max(P->max_dense, d.size);
-        P->m_active += d.size;
     }
     std::copy(cb, cb + 4, P->class_begin);
     for (const BlockDesc& d : P->ragged_all_h) {
         if (!is_active(d)) continue;
         P->ragged_h.push_back(d);
         P->max_ragged = std::max(P->max_ragged, d.size);
-        P->m_active += d.size;
     }
     if (!P->dense_h.empty())
         HIP_TRY(hipMemcpy(P->d_dense.p, P->dense_h.data(), sizeof(BlockDesc) * P->dense_h.size(), hipMemcpyHostToDevice));

@@ -18,6 +18,7 @@
 #include "../../include/viprs_hip.h"
 #include "kernels_common.h"
 #include "planner.h"
+#include "sweep_route.h"
 
 namespace viprs {
 
@@ -105,6 +106,85 @@ struct EventBracket {
     }
 };
 
+double host_clock_ms();                            // abi_plan.hip
+
+// The timing record of a plan's sweeps (viprs_plan_last_kernel_ms, viprs_plan_timing_history): a ring of the last kRing
+// sweeps.  Per sweep four HIP events {sweep start, sweep end, dense start, dense end}, recorded on the stream the kernels
+// are launched on, and the host clock (ms) at the record of the dense start event and behind the dense end event's
+// (which = 2).  The route of the sweep (sweep_route.h) says which of the events it records and who records the start.
+struct SweepTiming {
+    static constexpr int kRing = 256;
+    struct Slot {
+        DevEvent ev[4];
+        bool whole = false;                        // ev[0] .. ev[1] were recorded; otherwise ev[2] .. ev[3] bracket the whole sweep
+        bool dense = false;                        // ev[2] .. ev[3] were recorded
+        double t0 = 0.0, t1 = 0.0;
+    };
+    Slot ring[kRing];
+    hipStream_t stream = nullptr;
+    int64_t sweeps = 0;                            // sweeps recorded since the last reset
+    // The start event of the sweep being enqueued is recorded by the panel / grid launcher IMMEDIATELY in front of its first
+    // kernel launch (launcher_start): with an empty stream the event is reached at once, and whatever the host does between
+    // the record and the launch -- occupancy query, team split, launch gate, a scheduler hiccup -- would count as kernel time
+    bool armed = false;
+
+    Slot& slot(int64_t sweep) { return ring[sweep % kRing]; }
+    int create(hipStream_t s) {                    // every event up front: the launch path creates none
+        stream = s;
+        for (Slot& sl : ring)
+            for (DevEvent& e : sl.ev) HIP_TRY(hipEventCreate(&e.e));
+        return VIPRS_OK;
+    }
+    // the slot of the sweep being enqueued.  Its host stamps start at zero: a sweep that brackets nothing reports 0 for
+    // which = 2, not what an earlier sweep left in the slot
+    int open(bool whole_sweep_events, bool dense_bracketed) {
+        Slot& s = slot(sweeps);
+        s.whole = whole_sweep_events;
+        s.dense = dense_bracketed;
+        s.t0 = s.t1 = 0.0;
+        armed = false;
+        if (s.whole) HIP_TRY(hipEventRecord(s.ev[0].e, stream));
+        return VIPRS_OK;
+    }
+    void arm() { armed = true; }                   // the launcher records the start event
+    int start() {                                  // the caller records it, in front of the dense launcher
+        armed = false;
+        slot(sweeps).t0 = host_clock_ms();
+        HIP_TRY(hipEventRecord(slot(sweeps).ev[2].e, stream));
+        return VIPRS_OK;
+    }
+    int launcher_start() { return armed ? start() : VIPRS_OK; }      // (first launch of the sweep only: disarmed after)
+    int stop() {
+        HIP_TRY(hipEventRecord(slot(sweeps).ev[3].e, stream));
+        slot(sweeps).t1 = host_clock_ms();
+        return VIPRS_OK;
+    }
+    // behind the dense launcher: the end of its own bracket, where the sweep has one beside the whole sweep's
+    int dense_done() { return slot(sweeps).whole && slot(sweeps).dense ? stop() : VIPRS_OK; }
+    // behind the last launcher: ev[2] .. ev[3] close here when they stand for the whole sweep
+    int close() {
+        if (slot(sweeps).whole) HIP_TRY(hipEventRecord(slot(sweeps).ev[1].e, stream));
+        else { const int rc = stop(); if (rc != VIPRS_OK) return rc; }
+        sweeps++;
+        return VIPRS_OK;
+    }
+    void abandon() { armed = false; }              // a launcher failed: the sweep is not counted
+    void reset() { sweeps = 0; armed = false; }
+    // which: 0 = all kernels of the sweep, 1 = the dense bracket, 2 = host time inside the dense bracket
+    int elapsed(int64_t sweep, int which, double* ms) {
+        Slot& s = slot(sweep);
+        *ms = 0.0;
+        if (which == 2) { *ms = std::max(0.0, s.t1 - s.t0); return VIPRS_OK; }
+        const bool bracket = which == 1 || !s.whole;
+        if (bracket && !s.dense) return VIPRS_OK;
+        float t = 0.f;
+        HIP_TRY(hipEventSynchronize(s.ev[bracket ? 3 : 1].e));
+        HIP_TRY(hipEventElapsedTime(&t, s.ev[bracket ? 2 : 0].e, s.ev[bracket ? 3 : 1].e));
+        *ms = t;
+        return VIPRS_OK;
+    }
+};
+
 struct RidgeBlock;                                 // ridge.h: start and size of an LD block
 
 // ridge solve (abi_ridge.hip, ridge.h): the workspace of a plan, allocated by its first solve and reused by the later ones
@@ -164,11 +244,9 @@ struct viprs_plan {
     // lock-step fit of one model per chromosome drops the blocks of the chromosomes that have converged); the full lists:
     std::vector<viprs::BlockDesc> dense_all_h, ragged_all_h;
     int class_begin_all[4] = {0, 0, 0, 0};
-    int max_dense_all = 0, max_ragged_all = 0;
     viprs::DevBuf<viprs::BlockDesc> d_dense_all;   // what ensure_upper_storage converts (every block, active or not)
     bool filtered = false;
     uint64_t dense_gen = 0;                        // changes of the dense list (viprs_plan_set_active_blocks): maps indexed like it follow
-    int64_t m_active = 0;                          // SNPs of the blocks a sweep visits
     viprs::DevBuf<unsigned long long> d_granules;  // team hand-off granules (one row of 64 per panel of a team block)
     int64_t n_granule_rows = 0;
     viprs::DevBuf<int32_t> d_error;
@@ -200,18 +278,8 @@ struct viprs_plan {
     viprs::DevBuf<int64_t> d_grid_team_goff;
     viprs::DevBuf<unsigned long long> d_grid_gran;
     uint32_t grid_gen = 0;
-    // HIP-event ring: per sweep {sweep start, sweep end, panel start, panel end}, recorded on
-    // the stream the kernels are launched on
-    static constexpr int kRing = 256;
-    std::vector<hipEvent_t> ev;             // 4 * kRing
-    bool ev_dense_only[kRing] = {};         // ring slot: only [2] .. [3] were recorded (they bracket the whole sweep)
-    double host_t0[kRing] = {}, host_t1[kRing] = {};   // host clock (ms) at the start event's record and behind the end event's: which = 2
-    int64_t sweeps = 0;                     // sweeps recorded since the last timing reset
+    viprs::SweepTiming timing;                     // of the E-step sweeps
     viprs_state* scratch = nullptr;         // state used by the one-shot host-buffer calls
-    // start event of the sweep being enqueued, recorded by the panel / grid launcher IMMEDIATELY in front of its first kernel
-    // launch (record_start_event): with an empty stream the event is reached at once, and whatever the host does between the
-    // record and the launch -- occupancy query, team split, launch gate, a scheduler hiccup -- would count as kernel time
-    hipEvent_t pending_start_event = nullptr;
     // LD product (abi_dot.hip, ld_dot.h): its own tables over EVERY block of the plan (the product is not filtered by
     // viprs_plan_set_active_blocks), built by the first product; its own event pair
     bool dot_built = false;
@@ -299,8 +367,6 @@ int plan_create_generated(viprs_plan** out, int64_t m, const int32_t* lb, const 
 // waits for the previous gated launch on this device, `team_launch_done` records this one.  (Other PROCESSES on the
 // same device cannot be ordered from here: the bounded spins report VIPRS_EDEVICE instead of hanging.)
 int ensure_upper_storage(viprs_plan* P, bool mirrored);
-int record_start_event(viprs_plan* P);
-double host_clock_ms();
 int team_launch_gate(viprs_plan* P);
 int team_launch_done(viprs_plan* P);
 
@@ -321,9 +387,7 @@ int enqueue_dot(viprs_plan* P, int float_dtype, int n_cols, const void* dB, void
 int comm_reduce_on_stream(viprs_comm* C, double* d_vec, int n, int group, hipStream_t stream);
 
 // ---- kernel families (one translation unit per family and LD element type) ------------------------
-enum { kGenSpikeSlab = 0, kGenMixture = 1, kGenGrid = 2 };
-enum { kPanelSpikeSlab = 0, kPanelGridColumn = 1, kPanelMixture = 2, kPanelMixtureWide = 3 };
-enum { kBandSpikeSlab = 0, kBandGridColumn = 1, kBandMixture = 2 };
+// (the families and their model constants: sweep_route.h)
 
 // generic kernels over one block list: `dense` = the repacked dense blocks, otherwise the ragged blocks
 template <typename T, typename U> int launch_generic(viprs_plan* P, EStepArgs<T> A, int model, bool dense);

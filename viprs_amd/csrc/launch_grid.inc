@@ -105,7 +105,7 @@ int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A) {
         if (grid > 0) {
             void* params[] = {(void*)&A, (void*)&T};
             if (n_tb > 0) { const int rc = team_launch_gate(P); if (rc != VIPRS_OK) return rc; }
-            { const int rc = record_start_event(P); if (rc != VIPRS_OK) return rc; }      // (first launch of the sweep only: cleared after)
+            { const int rc = P->timing.launcher_start(); if (rc != VIPRS_OK) return rc; }      // (first launch of the sweep only: cleared after)
             HIP_TRY(hipLaunchKernel(kfn, dim3(grid), dim3(64 * kGridWaves), params, shmem, P->stream));
             if (n_tb > 0) { const int rc = team_launch_done(P); if (rc != VIPRS_OK) return rc; }
         }
@@ -113,7 +113,7 @@ int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A) {
         wg0 += n_twg;
         first = false;
     }
-    return record_start_event(P);           // (nothing was launched: an empty schedule)
+    return P->timing.launcher_start();           // (nothing was launched: an empty schedule)
 }
 
 template int launch_grid_mfma<GRID_U>(viprs_plan*, EStepArgs<float>);

@@ -108,7 +108,7 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
             shmem = std::max(shmem, lds_bytes(S.qcap[c]));
         }
     }
-    if (shmem == 0) return record_start_event(P);
+    if (shmem == 0) return P->timing.launcher_start();
     if (shmem > 160 * 1024) return fail(VIPRS_EUNSUPPORTED, "LD block too large for the LDS-resident panel kernel");
     if (shmem > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -179,7 +179,7 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
 
     void* params[] = {(void*)&S};
     if (team_wgs > 0) { const int rc = team_launch_gate(P); if (rc != VIPRS_OK) return rc; }
-    { const int rc = record_start_event(P); if (rc != VIPRS_OK) return rc; }      // (the sweep's start event: adjacent to the launch)
+    { const int rc = P->timing.launcher_start(); if (rc != VIPRS_OK) return rc; }      // (the sweep's start event: adjacent to the launch)
     HIP_TRY(hipLaunchKernel(kfn, dim3(grid), dim3(NW * 64), params, shmem, P->stream));
     if (team_wgs > 0) { const int rc = team_launch_done(P); if (rc != VIPRS_OK) return rc; }
     // (no commit launch: the member of a team that finishes a block last copies its staged eta / q into place)

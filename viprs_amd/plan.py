@@ -259,7 +259,8 @@ class LDPlan:
 
     def timing_history(self, which=0, capacity=256):
         """HIP-event durations (ms) of the most recent sweeps, oldest first (which: 0 = whole sweep,
-        1 = panel kernel(s) only)."""
+        1 = panel kernel(s) only, 2 = host ms inside that kernel's event bracket; a sweep that brackets no such kernel
+        reports 0 for 1 and 2)."""
         buf = (ctypes.c_double * capacity)()
         n = ctypes.c_int(0)
         L.check(L.lib.viprs_plan_timing_history(self.handle, int(which), buf, capacity, ctypes.byref(n)))
