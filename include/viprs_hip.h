@@ -637,6 +637,37 @@ int viprs_genotypes_score(viprs_genotypes* g, int float_dtype, int n_cols, const
 int viprs_genotypes_last_score_ms(viprs_genotypes* g, double* ms);
 int viprs_genotypes_last_counts_ms(viprs_genotypes* g, double* ms);
 
+/* ---- LD from genotypes: the correlation of the mean-imputed doses on the int8 matrix cores, in the compact upper store ----
+ * magenpy and plink compute LD for the reference; neither is part of the reference tree, so nothing here claims parity with
+ * them.  The definition below is the contract.
+ * For SNP j and sample s < n the .bed code gives a dose x_sj and a presence p_sj:
+ *   code 0: x = 2, p = 1;   code 2: x = 1, p = 1;   code 3: x = 0, p = 1;   code 1 (missing): x = 0, p = 0
+ * Per SNP, from the exact counts c0..c3:
+ *   nn_j = c0 + c2 + c3;  a_j = 2 c0 + c2;  q_j = 4 c0 + c2;  d_j = nn_j q_j - a_j^2 (int64)
+ *   w_j = sqrt((double)(nn_j d_j)), computed ON THE HOST in double and handed in (`w`): as for the dose tables, what is built
+ *   from the exact counts is built on the host
+ * Per pair, four exact integer sums over the samples:
+ *   S_ij = sum_s x_si x_sj;  U_ij = sum_s x_si p_sj;  U_ji = sum_s p_si x_sj;  N_ij = sum_s p_si p_sj
+ *   num_ij = nn_i nn_j S_ij - nn_i a_j U_ij - nn_j a_i U_ji + a_i a_j N_ij      (int64, exact)
+ *   r_ij   = (w_i == 0 || w_j == 0) ? 0.0 : (double)num_ij / (w_i * w_j)        (IEEE double, one rounding per operation, no fma)
+ * This is the Pearson correlation of the mean-imputed doses: unit diagonal, positive semi-definite over the full sample;
+ * a monomorphic or all-missing SNP gives 0.  The sums are integers accumulated exactly in int32 (v_mfma_i32_32x32x32_i8), so
+ * the order of summation is not part of the definition: the result equals a NumPy int64 evaluation with ==.
+ * OUTPUT element (`out_dtype`, ties to even as np.rint):
+ *   VIPRS_LD_F64: r;   VIPRS_LD_F32: (float)r;   VIPRS_LD_I8: rint(r 127) clamped to +-127;   VIPRS_LD_I16: rint(r 32767)
+ *   clamped to +-32767.  These are the stores' quantisation; dq_scale = 1 / max.
+ * n <= 2^19 keeps every term and the sum inside int64 (4 n^3 4 < 2^63); a larger n: VIPRS_EINVAL before any device work.
+ * WINDOWS.  right_end[j], j + 1 <= right_end[j] <= m, non-decreasing.  Row j of the store holds r_{j,k} for
+ * k = j + 1 .. right_end[j] - 1: indptr[j + 1] - indptr[j] = right_end[j] - j - 1, no diagonal.
+ * `data_host` receives rows [row0, row1) of the store, element indptr[row0] first; nothing else is written.  The caller
+ * slices the rows so that the device buffer and the download stay bounded.  Synchronous, on the object's own stream.
+ * NULL pointer, right_end not monotone or out of range, unknown dtype code, n > 2^19, row0 > row1 or rows outside [0, m]:
+ * VIPRS_EINVAL before any device work, outputs untouched.
+ *   viprs_genotypes_last_ld_ms   HIP-event time of the kernels of the last LD call on this object that launched any */
+int viprs_genotypes_ld(viprs_genotypes* g, int64_t row0, int64_t row1, const int64_t* right_end /* m */,
+                       const double* w /* m */, int out_dtype, void* data_host /* rows [row0,row1) of the store */);
+int viprs_genotypes_last_ld_ms(viprs_genotypes* g, double* ms);
+
 /* ---- measurement support: synthetic LD generated on the device (bench.py, tests) --------------
  * The "longrange" LD blocks of viprs_amd/utils/synthetic.py (the workload of BASELINE.json's configs, SURVEY.md 8d: the
  * reference gets its LD from magenpy stores, VIPRS.py:151-172, none of which exists here) written straight into a plan's

@@ -1,5 +1,7 @@
 // C ABI, genotype scoring (include/viprs_hip.h): packed PLINK .bed rows on the device, the per-SNP code counts and the
-// polygenic scores.  Score kernels: geno_score.h; the counts kernel and the kernel that sets the slots beyond n are here.
+// polygenic scores, and the LD matrix of the rows in the compact upper store.  Score kernels: geno_score.h; LD kernels:
+// geno_ld.h; the counts kernel and the kernel that sets the slots beyond n are here.
+#include "geno_ld.h"
 #include "geno_score.h"
 
 using namespace viprs;
@@ -15,6 +17,14 @@ struct viprs_genotypes {
     DevBuf<char> d_b, d_dose, d_work, d_scores;
     DevBuf<double> d_sums;
     EventBracket time_score, time_counts;
+    bool counts_on_device = false;                 // d_counts holds the counts of the rows as they are now
+    // LD (viprs_genotypes_ld): nn, a and the tiles free of missing codes follow from the counts, once per upload
+    bool ld_tables_built = false;
+    std::vector<uint8_t> tile_clean;               // per tile of kLdTile SNPs
+    DevBuf<int64_t> d_nn, d_a, d_right_end, d_indptr, d_pairs;
+    DevBuf<double> d_w;
+    DevBuf<char> d_ld_out;
+    EventBracket time_ld;
     ~viprs_genotypes() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
@@ -128,6 +138,76 @@ int score_typed(viprs_genotypes* G, int n_cols, bool with_dose) {
     return G->time_score.stop(G->stream);
 }
 
+// nn_j, a_j and the clean tiles of the LD kernels, from the device counts: those of the caller's last counts call when the
+// rows have not changed since, otherwise the counts kernel runs here (the caller's timing of it is not touched)
+int ensure_ld_tables(viprs_genotypes* G) {
+    if (G->ld_tables_built || G->m == 0) return VIPRS_OK;
+    const size_t m = (size_t)G->m;
+    std::vector<int64_t> c(m * 4, 0);
+    if (G->n > 0) {
+        if (!G->counts_on_device) {
+            HIP_TRY(G->d_counts.reserve(m * 4));
+            geno_counts_kernel<<<dim3((unsigned)((G->m + 3) / 4)), dim3(256), 0, G->stream>>>(G->d_rows.p, G->m, G->n,
+                                                                                             G->stride, G->d_counts.p);
+            HIP_TRY(hipGetLastError());
+            G->counts_on_device = true;
+        }
+        HIP_TRY(hipMemcpyAsync(c.data(), G->d_counts.p, m * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, G->stream));
+        HIP_TRY(hipStreamSynchronize(G->stream));
+    }
+    std::vector<int64_t> nn(m), a(m);
+    std::vector<uint8_t> clean((m + kLdTile - 1) / kLdTile, 1);
+    for (size_t j = 0; j < m; ++j) {
+        nn[j] = c[j * 4] + c[j * 4 + 2] + c[j * 4 + 3];
+        a[j] = 2 * c[j * 4] + c[j * 4 + 2];
+        if (c[j * 4 + 1] != 0) clean[j / kLdTile] = 0;
+    }
+    HIP_TRY(G->d_nn.reserve(m));
+    HIP_TRY(G->d_a.reserve(m));
+    HIP_TRY(hipMemcpyAsync(G->d_nn.p, nn.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, G->stream));
+    HIP_TRY(hipMemcpyAsync(G->d_a.p, a.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, G->stream));
+    HIP_TRY(hipStreamSynchronize(G->stream));
+    G->tile_clean.swap(clean);
+    G->ld_tables_built = true;
+    return VIPRS_OK;
+}
+
+// Everything `viprs_genotypes_ld` puts on the stream: the uploads of the call's tables, the kernels between the LD event pair,
+// the download.  Nothing is synchronised here: the caller drains the stream whatever this returns, because the uploads read
+// pageable host memory of the caller's frame
+int enqueue_ld(viprs_genotypes* G, int64_t row0, int64_t row1, const int64_t* right_end, const double* w, int out_dtype,
+               const std::vector<int64_t>& indptr, const std::vector<int64_t>& pairs, size_t n_clean, void* data_host) {
+    const size_t m = (size_t)G->m;
+    const size_t out_bytes = (size_t)(indptr[(size_t)row1] - indptr[(size_t)row0]) * ld_elem_size(out_dtype);
+    HIP_TRY(hipMemcpyAsync(G->d_right_end.p, right_end, m * sizeof(int64_t), hipMemcpyHostToDevice, G->stream));
+    HIP_TRY(hipMemcpyAsync(G->d_indptr.p, indptr.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, G->stream));
+    HIP_TRY(hipMemcpyAsync(G->d_w.p, w, m * sizeof(double), hipMemcpyHostToDevice, G->stream));
+    HIP_TRY(hipMemcpyAsync(G->d_pairs.p, pairs.data(), pairs.size() * sizeof(int64_t), hipMemcpyHostToDevice, G->stream));
+    GenoLdArgs A;
+    A.rows = G->d_rows.p;
+    A.right_end = G->d_right_end.p;
+    A.indptr = G->d_indptr.p;
+    A.nn = G->d_nn.p;
+    A.a = G->d_a.p;
+    A.w = G->d_w.p;
+    A.pairs = nullptr;
+    A.out = G->d_ld_out.p;
+    A.m = G->m;
+    A.n = G->n;
+    A.stride = G->stride;
+    A.row0 = row0;
+    A.row1 = row1;
+    int rc = G->time_ld.start(G->stream);
+    if (rc != VIPRS_OK) return rc;
+    rc = launch_geno_ld(G->stream, out_dtype, A, G->d_pairs.p, (int64_t)n_clean, G->d_pairs.p + n_clean,
+                        (int64_t)(pairs.size() - n_clean));
+    if (rc != VIPRS_OK) return rc;
+    rc = G->time_ld.stop(G->stream);
+    if (rc != VIPRS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(data_host, G->d_ld_out.p, out_bytes, hipMemcpyDeviceToHost, G->stream));
+    return VIPRS_OK;
+}
+
 }  // namespace
 }  // namespace viprs
 
@@ -172,6 +252,8 @@ int viprs_genotypes_upload_rows(viprs_genotypes* G, int64_t first_row, int64_t n
     if (n_rows == 0 || G->n == 0) return VIPRS_OK;
     if (!bed_rows) return fail(VIPRS_EINVAL, "null host buffer");
     HIP_TRY(hipSetDevice(G->device));
+    G->counts_on_device = false;                   // (counts and LD tables follow the rows: rebuilt by the next call)
+    G->ld_tables_built = false;
     uint8_t* dst = G->d_rows.p + (size_t)first_row * (size_t)G->stride;
     if (G->stride == G->file_stride)
         HIP_TRY(hipMemcpyAsync(dst, bed_rows, (size_t)n_rows * (size_t)G->stride, hipMemcpyHostToDevice, G->stream));
@@ -207,6 +289,7 @@ int viprs_genotypes_counts(viprs_genotypes* G, int64_t* counts) {
     if (rc != VIPRS_OK) return rc;
     HIP_TRY(hipMemcpyAsync(counts, G->d_counts.p, bytes, hipMemcpyDeviceToHost, G->stream));
     HIP_TRY(hipStreamSynchronize(G->stream));
+    G->counts_on_device = true;
     return VIPRS_OK;
 }
 
@@ -237,6 +320,64 @@ int viprs_genotypes_score(viprs_genotypes* G, int float_dtype, int n_cols, const
     HIP_TRY(hipMemcpyAsync(scores_host, G->d_scores.p, out_bytes, hipMemcpyDeviceToHost, G->stream));
     HIP_TRY(hipStreamSynchronize(G->stream));
     return VIPRS_OK;
+}
+
+int viprs_genotypes_ld(viprs_genotypes* G, int64_t row0, int64_t row1, const int64_t* right_end, const double* w, int out_dtype,
+                       void* data_host) {
+    // every argument check comes before any device work
+    if (out_dtype != VIPRS_LD_I8 && out_dtype != VIPRS_LD_I16 && out_dtype != VIPRS_LD_F32 && out_dtype != VIPRS_LD_F64)
+        return fail(VIPRS_EINVAL, "bad LD output dtype code: int8, int16, float32 or float64");
+    if (row0 > row1) return fail(VIPRS_EINVAL, "row0 must not exceed row1");
+    if (!right_end) return fail(VIPRS_EINVAL, "null right_end");
+    if (!w) return fail(VIPRS_EINVAL, "null w");
+    if (!data_host) return fail(VIPRS_EINVAL, "null host buffer");
+    if (!G) return fail(VIPRS_EINVAL, "null genotypes");
+    if (G->n > kLdMaxSamples)
+        return fail(VIPRS_EINVAL, "n_samples must not exceed 2^19 = 524288: beyond it the numerator leaves int64");
+    if (row0 < 0 || row1 > G->m) return fail(VIPRS_EINVAL, "rows out of range");
+    for (int64_t j = 0; j < G->m; ++j) {
+        if (right_end[j] < j + 1 || right_end[j] > G->m) return fail(VIPRS_EINVAL, "right_end[j] must lie in [j + 1, m]");
+        if (j > 0 && right_end[j] < right_end[j - 1]) return fail(VIPRS_EINVAL, "right_end must be non-decreasing");
+    }
+    if (row0 == row1) return VIPRS_OK;
+    const size_t m = (size_t)G->m;
+    std::vector<int64_t> indptr(m + 1, 0);
+    for (size_t j = 0; j < m; ++j) indptr[j + 1] = indptr[j] + (right_end[j] - (int64_t)j - 1);
+    const int64_t n_out = indptr[(size_t)row1] - indptr[(size_t)row0];
+    if (n_out == 0) return VIPRS_OK;
+    HIP_TRY(hipSetDevice(G->device));
+    int rc = ensure_ld_tables(G);
+    if (rc != VIPRS_OK) return rc;
+    // tile pairs (I, J), J >= I, that meet the window of rows [row0, row1); right_end is monotone, so the last row of the
+    // tile inside the range reaches furthest.  Clean pairs first, then the general ones
+    std::vector<int64_t> pairs_clean, pairs_general;
+    for (int64_t I = row0 / kLdTile; I * kLdTile < row1; ++I) {
+        const int64_t last = std::min<int64_t>((I + 1) * kLdTile, row1) - 1;
+        const int64_t J1 = (right_end[last] - 1) / kLdTile;
+        for (int64_t J = I; J <= J1; ++J)
+            (G->tile_clean[(size_t)I] && G->tile_clean[(size_t)J] ? pairs_clean : pairs_general).push_back((I << 32) | J);
+    }
+    const size_t n_clean = pairs_clean.size();
+    pairs_clean.insert(pairs_clean.end(), pairs_general.begin(), pairs_general.end());
+    const size_t out_bytes = (size_t)n_out * ld_elem_size(out_dtype);
+    // (a failed allocation leaves its buffer empty, dev_buf.h: the next call allocates again)
+    HIP_TRY(G->d_right_end.reserve(m));
+    HIP_TRY(G->d_indptr.reserve(m + 1));
+    HIP_TRY(G->d_w.reserve(m));
+    HIP_TRY(G->d_pairs.reserve(pairs_clean.size()));
+    if (G->d_ld_out.reserve(out_bytes) != hipSuccess)
+        return fail(VIPRS_ENOMEM, "no device memory for the rows of the LD store: give a smaller row range");
+    rc = enqueue_ld(G, row0, row1, right_end, w, out_dtype, indptr, pairs_clean, n_clean, data_host);
+    // on the error paths too: the uploads read `indptr`, `pairs_clean` and the caller's arrays until the stream is drained
+    const hipError_t drained = hipStreamSynchronize(G->stream);
+    if (rc != VIPRS_OK) return rc;
+    HIP_TRY(drained);
+    return VIPRS_OK;
+}
+
+int viprs_genotypes_last_ld_ms(viprs_genotypes* G, double* ms) {
+    if (!G || !ms) return fail(VIPRS_EINVAL, "null argument");
+    return G->time_ld.elapsed(G->device, ms, "no timed LD call yet");
 }
 
 int viprs_genotypes_last_counts_ms(viprs_genotypes* G, double* ms) {

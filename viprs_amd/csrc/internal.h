@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/viprs_hip.h"
+#include "dev_buf.h"
 #include "kernels_common.h"
 #include "planner.h"
 #include "sweep_route.h"
@@ -61,18 +62,6 @@ struct SchedConfig {
 SchedConfig& sched_config();                       // process-wide, read from the environment at plan creation
 constexpr int kClassWaves[3] = {4, 4, 4};
 constexpr int kPlanCounters = 32;                  // work-queue heads of a plan (d_counters), zeroed by every sweep's prologue
-
-template <typename V> struct DevBuf {
-    V* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        n = count;
-        if (count == 0) return hipSuccess;
-        return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(V));
-    }
-};
 
 struct DevEvent {
     hipEvent_t e = nullptr;

@@ -180,6 +180,50 @@ class ArrayDataLoader:
             total = parts[c].copy() if total is None else total + parts[c]
         return total
 
+    # ---- genotypes: the LD of the loader's own panel --------------------------------------------------------------------
+    def compute_ld(self, estimator=("sample",), dtype=np.float32, max_bytes=1 << 30):
+        """LD of every chromosome that has genotypes, from the genotypes (`DeviceGenotypes.ld`: int8 matrix cores; on the
+        host without a device): ``self.ld[c]`` becomes an `LDArrays` with the compact upper-triangular form, the quantisation
+        scale of `dtype` (int8, int16, float32, float64) and the panel's sample size.  `estimator`: one of
+        `viprs_amd.genotypes.ld_windows`, or ``{chromosome: estimator}``; ``("windowed_bp", distance)`` takes the positions
+        from the chromosome's SNP table (``POS``).  A model built on the loader afterwards reads this LD like any other;
+        `write_ld_stores` saves it.  Returns ``self.ld``."""
+        from .genotypes import ld_dq_scale, ld_windows
+        if not self.genotype:
+            raise ValueError("this loader holds no genotypes.  Remedy: ArrayDataLoader(..., genotype={chromosome: "
+                             ".bed prefix | (packed_rows, n) | DeviceGenotypes}).")
+        self.ld_estimator = dict(getattr(self, "ld_estimator", {}))
+        for c in sorted(self.genotype):
+            g = self._open_genotypes(c)
+            if c in self.shapes and self.shapes[c] != g.m:
+                raise ValueError(f"chromosome {c}: {g.m} genotyped SNPs against {self.shapes[c]} SNPs of the summary "
+                                 "statistics: the LD would not line up with them (subset the genotypes to the SNPs of "
+                                 "the summary statistics, in their order)")
+            est = estimator[c] if isinstance(estimator, dict) else estimator
+            est = (est,) if isinstance(est, str) else tuple(est)
+            if est[0] == "windowed_bp" and len(est) == 2:
+                if not self.snp_table or c not in self.snp_table or "POS" not in self.snp_table[c]:
+                    raise ValueError(f"chromosome {c}: ('windowed_bp', distance) needs POS in the SNP table")
+                est = est + (self.snp_table[c]["POS"],)
+            indptr, data = g.ld(ld_windows(est, g.m), dtype=dtype, max_bytes=max_bytes)
+            self.ld[c] = LDArrays(upper=(np.arange(1, g.m + 1, dtype=np.int32), indptr, data),
+                                  dq_scale=ld_dq_scale(dtype), sample_size=int(g.n))
+            self.ld_estimator[c] = est[0]
+        return self.ld
+
+    def write_ld_stores(self, ld_dir, **kw):
+        """The LD of `compute_ld` as one zarr store per chromosome under `ld_dir` (``chr_<c>``), with the attributes
+        `ZarrLDMatrix` reads back: ``{chromosome: path}``.  `kw` goes to `viprs_amd.io.zarr_ld.write_ld_store`."""
+        import os
+        from .io.zarr_ld import write_ld_store
+        paths = {}
+        for c, name in sorted(getattr(self, "ld_estimator", {}).items()):
+            lb, ip, data = self.ld[c]._forms[False]
+            paths[c] = os.path.join(str(ld_dir), f"chr_{c}")
+            write_ld_store(paths[c], ip, data, attrs={"Chromosome": c, "LD estimator": name,
+                                                      "Sample size": self.ld[c].sample_size}, **kw)
+        return paths
+
     def close_genotypes(self):
         for g in self._own_genotypes:
             g.close()

@@ -14,6 +14,8 @@ dose table, built here on the host in double from the exact counts and rounded o
 * ``dose_table``         the tables from the counts;
 * ``DeviceGenotypes``    the rows on a HIP device (`viprs_genotypes_*`): ``counts``, ``dose_table``, ``score``;
 * ``HostGenotypes``      the same surface over `score_host` (what a loader uses when no device is visible);
+* ``ld_host``            the LD matrix of the rows from the definition (`viprs_genotypes_ld`), ``ld_windows`` the windows of
+                         an estimator; both classes have ``ld()``;
 * ``open_genotypes``     a loader's genotype entry -- one of the two above, ``(packed_rows, n)`` or a .bed prefix -- opened;
 * ``model_predict``      ``predict()`` of the model classes.
 """
@@ -103,12 +105,180 @@ def score_host(packed_rows, n, B, D=None):
     return out[:, 0] if B.ndim == 1 else out
 
 
+# ---- LD from genotypes (include/viprs_hip.h, viprs_genotypes_ld) ----------------------------------------------------------
+LD_MAX_SAMPLES = 1 << 19                 # 4 n^3 4 < 2^63: the numerator stays inside int64
+LD_DTYPES = {np.dtype(np.int8): 127.0, np.dtype(np.int16): 32767.0, np.dtype(np.float32): None, np.dtype(np.float64): None}
+LD_ESTIMATORS = ("sample", "windowed", "windowed_bp", "block")
+_LD_TILE = 64                            # kLdTile (viprs_amd/csrc/geno_ld.h): the rows of a device call are whole tiles
+_LD_HOST_SLAB = 256                      # rows `ld_host` computes at a time
+
+
+def _ld_dtype(dtype):
+    T = np.dtype(dtype)
+    if T not in LD_DTYPES:
+        raise ValueError(f"LD dtype: int8, int16, float32 or float64, got {T}")
+    return T
+
+
+def ld_dq_scale(dtype):
+    """What turns a stored element into a correlation: 1 / 127, 1 / 32767, or 1 for the float types."""
+    q = LD_DTYPES[_ld_dtype(dtype)]
+    return 1.0 if q is None else 1.0 / q
+
+
+def ld_stats(counts):
+    """``(nn, a, w)`` of the definition from the exact (m, 4) code counts: non-missing samples and dose sums (int64), and
+    ``w = sqrt((double)(nn d))``, ``d = nn q - a^2``, ``q = 4 c0 + c2`` (float64; 0 for a monomorphic or all-missing SNP)."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+    nn = c[:, 0] + c[:, 2] + c[:, 3]
+    a = 2 * c[:, 0] + c[:, 2]
+    q = 4 * c[:, 0] + c[:, 2]
+    d = nn * q - a * a
+    return nn, a, np.sqrt((nn * d).astype(np.float64))
+
+
+def _check_right_end(right_end, m):
+    """The windows of the compact upper store as (m,) int64: ``j + 1 <= right_end[j] <= m``, non-decreasing."""
+    re = np.ascontiguousarray(right_end, dtype=np.int64)
+    if re.shape != (int(m),):
+        raise ValueError(f"right_end: ({int(m)},), got {re.shape}")
+    if m and (np.any(re < np.arange(1, m + 1)) or np.any(re > m)):
+        raise ValueError("right_end[j] must lie in [j + 1, m]")
+    if m and np.any(np.diff(re) < 0):
+        raise ValueError("right_end must be non-decreasing")
+    return re
+
+
+def ld_indptr(right_end):
+    """Row pointers of the compact upper store: ``indptr[j + 1] - indptr[j] = right_end[j] - j - 1`` (no diagonal)."""
+    re = np.asarray(right_end, dtype=np.int64)
+    return np.concatenate([[0], np.cumsum(re - np.arange(1, re.shape[0] + 1))]).astype(np.int64)
+
+
+def ld_windows(estimator, m):
+    """``right_end`` (m,) int64 of an LD estimator:
+
+    ``("sample",)``                            every pair
+    ``("windowed", n_snps)``                   the `n_snps` SNPs that follow
+    ``("windowed_bp", distance, positions)``   the SNPs within `distance` base pairs; `positions`: the .bim's POS, sorted
+                                               (SNPs at one position are inside each other's window)
+    ``("block", boundaries)``                  block starts (0 and m may be left out); a row ends with its block"""
+    m = int(m)
+    if isinstance(estimator, str):
+        estimator = (estimator,)
+    kind = estimator[0]
+    j = np.arange(m, dtype=np.int64)
+    if kind == "sample" and len(estimator) == 1:
+        re = np.full(m, m, dtype=np.int64)
+    elif kind == "windowed" and len(estimator) == 2:
+        k = int(estimator[1])
+        if k < 0:
+            raise ValueError("windowed: the SNP count must not be negative")
+        re = np.minimum(j + 1 + k, m)
+    elif kind == "windowed_bp" and len(estimator) == 3:
+        pos = np.asarray(estimator[2], dtype=np.int64)
+        if pos.shape != (m,):
+            raise ValueError(f"windowed_bp: ({m},) positions, got {pos.shape}")
+        if np.any(np.diff(pos) < 0):
+            raise ValueError("windowed_bp: the positions must be sorted")
+        if int(estimator[1]) < 0:
+            raise ValueError("windowed_bp: the distance must not be negative")
+        re = np.searchsorted(pos, pos + int(estimator[1]), side="right").astype(np.int64)
+    elif kind == "block" and len(estimator) == 2:
+        b = np.asarray(estimator[1], dtype=np.int64).reshape(-1)
+        if b.size and (b.min() < 0 or b.max() > m):
+            raise ValueError(f"block: boundaries must lie in [0, {m}]")
+        b = np.unique(np.concatenate([[0], b, [m]]))
+        re = b[np.searchsorted(b, j, side="right")] if m else np.zeros(0, dtype=np.int64)
+    else:
+        raise ValueError(f"LD estimator {estimator!r}: ('sample',), ('windowed', n_snps), "
+                         "('windowed_bp', distance, positions) or ('block', boundaries)")
+    return _check_right_end(re, m)
+
+
+def _ld_planes(packed_rows, n):
+    """(dose, presence) of the rows as float64 (k, n): integers, so that every product below is exact."""
+    codes = unpack_codes(packed_rows, n)
+    x = np.where(codes == 0, 2.0, np.where(codes == 2, 1.0, 0.0))
+    return x, (codes != 1).astype(np.float64)
+
+
+def ld_block_host(rows_i, rows_j, n, stats_i=None, stats_j=None):
+    """``r`` (len(rows_i), len(rows_j)) float64 between two sets of packed rows, straight from the definition.  The four sums
+    are float64 matrix products of small integers (every partial sum is an integer below 2^53, hence exact in any order),
+    `num` is int64.  `stats_*`: ``ld_stats`` of the rows when the caller has them."""
+    pi, n = _check_rows(rows_i, n)
+    pj, _ = _check_rows(rows_j, n)
+    if n > LD_MAX_SAMPLES:
+        raise ValueError(f"n = {n} samples: LD needs n <= 2^19 = {LD_MAX_SAMPLES} (beyond it the numerator leaves int64)")
+    nn_i, a_i, w_i = stats_i if stats_i is not None else ld_stats(counts_host(pi, n))
+    nn_j, a_j, w_j = stats_j if stats_j is not None else ld_stats(counts_host(pj, n))
+    xi, qi = _ld_planes(pi, n)
+    xj, qj = _ld_planes(pj, n)
+    S = np.rint(xi @ xj.T).astype(np.int64)
+    U_ij = np.rint(xi @ qj.T).astype(np.int64)
+    U_ji = np.rint(qi @ xj.T).astype(np.int64)
+    N = np.rint(qi @ qj.T).astype(np.int64)
+    num = ((nn_i[:, None] * nn_j[None, :]) * S - (nn_i[:, None] * a_j[None, :]) * U_ij
+           - (a_i[:, None] * nn_j[None, :]) * U_ji + (a_i[:, None] * a_j[None, :]) * N)
+    den = w_i[:, None] * w_j[None, :]
+    live = den != 0.0                                  # (w >= 0 and finite: the product is 0 only when a factor is)
+    return np.where(live, num.astype(np.float64) / np.where(live, den, 1.0), 0.0)
+
+
+def _ld_quantize(r, dtype):
+    """A float64 correlation as a stored element: itself, ``(float)r``, or ``rint(r max)`` clamped to ``+-max``."""
+    T = _ld_dtype(dtype)
+    q = LD_DTYPES[T]
+    if q is None:
+        return np.asarray(r, dtype=np.float64).astype(T)
+    return np.clip(np.rint(np.asarray(r, dtype=np.float64) * q), -q, q).astype(T)
+
+
+def ld_host(packed_rows, n, right_end, dtype=np.float32):
+    """``(indptr, data)``: the LD of the rows inside the windows `right_end` as the compact upper store, in NumPy int64 and
+    float64 from the definition in ``include/viprs_hip.h``.  The CPU fallback and the yardstick of the device kernels."""
+    p, n = _check_rows(packed_rows, n)
+    m = p.shape[0]
+    T = _ld_dtype(dtype)
+    if n > LD_MAX_SAMPLES:
+        raise ValueError(f"n = {n} samples: LD needs n <= 2^19 = {LD_MAX_SAMPLES} (beyond it the numerator leaves int64)")
+    re = _check_right_end(right_end, m)
+    ip = ld_indptr(re)
+    data = np.zeros(int(ip[-1]), dtype=T)
+    nn, a, w = ld_stats(counts_host(p, n))
+    for r0 in range(0, m, _LD_HOST_SLAB):
+        r1 = min(m, r0 + _LD_HOST_SLAB)
+        c1 = int(re[r1 - 1])
+        if ip[r1] == ip[r0]:
+            continue
+        R = ld_block_host(p[r0:r1], p[r0 + 1:c1], n, (nn[r0:r1], a[r0:r1], w[r0:r1]),
+                          (nn[r0 + 1:c1], a[r0 + 1:c1], w[r0 + 1:c1]))
+        for j in range(r0, r1):
+            data[ip[j]:ip[j + 1]] = _ld_quantize(R[j - r0, j - r0:int(re[j]) - r0 - 1], T)
+    return ip, data
+
+
 class _Genotypes:
     """What the two genotype classes share: everything that follows from the counts."""
 
     n = m = 0
 
     def counts(self):
+        raise NotImplementedError
+
+    def _right_end(self, window):
+        """`window` of `ld`: None (every pair), an estimator of `ld_windows`, or the (m,) right ends themselves."""
+        if window is None:
+            return ld_windows(("sample",), self.m)
+        if isinstance(window, str) or (isinstance(window, tuple) and window and isinstance(window[0], str)):
+            return ld_windows(window, self.m)
+        return _check_right_end(window, self.m)
+
+    def ld(self, window=None, dtype=np.float32, max_bytes=1 << 30):
+        """``(indptr, data)``: the LD matrix of the SNPs inside `window` as the compact upper store in `dtype` (int8, int16,
+        float32, float64; `ld_dq_scale` turns an element into a correlation).  On the device the rows are computed in ranges
+        of at most `max_bytes` of the store (a tile row of 64 SNPs at least)."""
         raise NotImplementedError
 
     def allele_frequency(self):
@@ -158,6 +328,9 @@ class HostGenotypes(_Genotypes):
         B2, D, T, flat = self._score_args(B, dose, float_precision)
         s = score_host(self.rows, self.n, B2, D).astype(T)
         return s[:, 0] if flat else s
+
+    def ld(self, window=None, dtype=np.float32, max_bytes=1 << 30):
+        return ld_host(self.rows, self.n, self._right_end(window), dtype)
 
     def close(self):
         pass
@@ -210,6 +383,53 @@ class DeviceGenotypes(_Genotypes):
                                             None if D is None else D.ctypes.data_as(ctypes.c_void_p),
                                             out.ctypes.data_as(ctypes.c_void_p)))
         return out[:, 0] if flat else out
+
+    def ld_rows(self, row0, row1, right_end, w, out):
+        """Rows ``[row0, row1)`` of the compact upper store of the windows `right_end` into `out` (`viprs_genotypes_ld`): a
+        C-contiguous array of an LD dtype with ``indptr[row1] - indptr[row0]`` elements.  `w`: ``ld_stats(counts)[2]``."""
+        L = self._L
+        code = {np.dtype(np.int8): L.LD_I8, np.dtype(np.int16): L.LD_I16, np.dtype(np.float32): L.LD_F32,
+                np.dtype(np.float64): L.LD_F64}[_ld_dtype(out.dtype)]
+        re = np.ascontiguousarray(right_end, dtype=np.int64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if re.shape != (self.m,) or w.shape != (self.m,):
+            raise ValueError(f"right_end and w: ({self.m},) each")
+        if not 0 <= row0 <= row1 <= self.m:
+            raise ValueError(f"rows [{row0}, {row1}) of {self.m}")
+        ip = ld_indptr(re)
+        if not out.flags.c_contiguous or not out.flags.writeable or out.size != int(ip[row1] - ip[row0]):
+            raise ValueError(f"out: a writeable C-contiguous array of {int(ip[row1] - ip[row0])} elements")
+        spare = np.zeros(1, dtype=out.dtype)           # (an empty array may have no address to hand over)
+        L.check(L.lib.viprs_genotypes_ld(self.handle, int(row0), int(row1), re.ctypes.data_as(ctypes.c_void_p),
+                                         w.ctypes.data_as(ctypes.c_void_p), code,
+                                         (out if out.size else spare).ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def ld(self, window=None, dtype=np.float32, max_bytes=1 << 30):
+        T = _ld_dtype(dtype)
+        re = self._right_end(window)
+        if self.n > LD_MAX_SAMPLES:
+            raise ValueError(f"n = {self.n} samples: LD needs n <= 2^19 = {LD_MAX_SAMPLES} (beyond it the numerator "
+                             "leaves int64)")
+        ip = ld_indptr(re)
+        data = np.zeros(int(ip[-1]), dtype=T)
+        w = ld_stats(self.counts())[2]
+        budget = max(int(max_bytes) // T.itemsize, 1)
+        r0 = 0
+        while r0 < self.m:                             # whole tile rows while they fit the budget, one at least
+            r1 = min(self.m, r0 + _LD_TILE)
+            while r1 < self.m and ip[min(self.m, r1 + _LD_TILE)] - ip[r0] <= budget:
+                r1 = min(self.m, r1 + _LD_TILE)
+            if ip[r1] > ip[r0]:
+                self.ld_rows(r0, r1, re, w, data[ip[r0]:ip[r1]])
+            r0 = r1
+        return ip, data
+
+    def last_ld_ms(self):
+        """HIP-event time (ms) of the kernels of the last device call of `ld` / `ld_rows` on this object."""
+        ms = ctypes.c_double(0.0)
+        self._L.check(self._L.lib.viprs_genotypes_last_ld_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
 
     def last_score_ms(self):
         """HIP-event time (ms) of the kernels of the last `score` on this object."""
