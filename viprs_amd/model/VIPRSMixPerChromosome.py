@@ -27,8 +27,10 @@ import logging
 import numpy as np
 
 from ..utils.optim import OptimizeResult
+from ._lockstep import RESTART, keeps_going, run_rounds
+from ._lockstep_mix import LockstepMixEM
+from ._per_chromosome import PerChromosomeGroups
 from .VIPRSMix import VIPRSMix
-from .VIPRSPerChromosome import PerChromosomeGroups
 
 logger = logging.getLogger(__name__)
 
@@ -80,12 +82,6 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
             for k, v in saved.items():
                 setattr(self, k, v)
 
-    def _theta0_of(self, c, theta_0):
-        t0 = theta_0
-        if isinstance(theta_0, dict) and theta_0 and all(k in self._gindex for k in theta_0):
-            t0 = theta_0.get(c)                                    # {chromosome: theta_0}
-        return dict(t0) if t0 else None                            # (`_merge_theta` writes into its argument)
-
     # ---- variational state of one chromosome (VIPRS.py:330-359 with (m, K) arrays) -----------------------------------------
     def _init_chromosome_state(self, c, rec):
         T, shp = self._T, self._shape(c)
@@ -109,7 +105,7 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
         VIPRS.py:1025-1037): its hyper-parameters are drawn again, its arrays start over; the other chromosomes keep theirs."""
         c = self.groups[self._cur]
         logger.info("Chromosome %s: restarting with sigma_epsilon fixed.", c)
-        self.initialize_theta(self._theta0_of(c, theta_0))
+        self.initialize_theta(self._theta0_for(c, theta_0))
         if self._e_step_fn is None:
             self._pull_state()
         if c in self.shapes:
@@ -172,11 +168,7 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
             ds = self._dstate["*"]
             ds.sums_mixture_groups_begin(a, [float(1.0 + self._T.type(self._lambda_group[g])) for g in a])
             s, reduced = ds.sums_mixture_groups_end(), self._device_reduce
-        if self.comm.world_size > 1 and not reduced:
-            tot = self.comm.allreduce_sum(np.ascontiguousarray(s[:, :-1]).ravel()).reshape(len(a), -1)
-            mx = self.comm.allreduce_max(np.ascontiguousarray(s[:, -1]))
-            s = np.column_stack([tot, mx])
-        return s
+        return self._all_rank_sums(s, reduced)
 
     # ---- the fit ----------------------------------------------------------------------------------------------------------------
     def fit(self, max_iter=1000, theta_0=None, param_0=None, continued=False, disable_pbar=True, min_iter=3,
@@ -197,7 +189,7 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
         # ---- hyper-parameters of every model as VIPRSMix.initialize_theta leaves them (several ranks: rank 0's draws) ----
         for g, c in enumerate(self.groups):
             with self._as_model(g):
-                self.initialize_theta(self._theta0_of(c, theta_0))
+                self.initialize_theta(self._theta0_for(c, theta_0))
                 self.init_optim_meta()
         # ---- standard start of every chromosome + its initial ELBO ----
         self.var_mu, self.var_tau, self.var_gamma, self._log_var_tau = {}, {}, {}, {}
@@ -248,8 +240,6 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
 
     # ---- the same loop with the host side as array operations over the active models ----------------------------------------
     def _iterate_vector(self, max_iter, theta_0, min_iter, f_abs_tol, x_abs_tol, patience, on_iteration):
-        from ._lockstep import RESTART
-        from ._lockstep_mix import LockstepMixEM
         M, G, T = self._models, len(self.groups), self._T
         th = [dict(pi=M[g]["pi"], sigma_epsilon=M[g]["sigma_epsilon"], tau_beta=M[g]["tau_beta"],
                    lam=T.type(self._lambda_group[g]), fixed=M[g]["fix_params"]) for g in range(G)]
@@ -263,12 +253,7 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
             rec["pi"], rec["sigma_epsilon"], rec["tau_beta"] = em.theta(g)
             rec["_sigma_g"], rec["_max_eta_diff"] = em.sigma_g[g], float(em.max_eta_diff[g])
 
-        active = np.arange(G)
-        for i in range(1, max_iter + 1):
-            if active.size == 0:
-                break
-            a = active
-            em.mark_e_step(a)
+        def sweep(a):
             if self._e_step_fn is None:
                 ds = self._dstate["*"]
                 ds.prep_mixture_groups(em.prep_rows(a))
@@ -278,16 +263,13 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
                 for g in a:
                     sync_model(int(g))
                 self._sweep_models(a)
-            code = em.update(a, self._model_sums(a), i)
+
+        def settle(a, code, i):
             for g in a:
                 h = M[g]["history"]
                 h["ELBO"].append(float(em.elbos[g]))
                 if self.tracked_params:
-                    pi, sig, tau = em.theta(g)
-                    for t in self.tracked_params:
-                        h[t].append({"pi": lambda: np.sum(pi), "heritability": lambda: em.sigma_g[g] / (em.sigma_g[g] + sig),
-                                     "sigma_epsilon": lambda: sig, "tau_beta": lambda: tau, "sigma_g": lambda: em.sigma_g[g],
-                                     "max_eta_diff": lambda: float(em.max_eta_diff[g])}[t]())
+                    self._append_tracked(h, em.theta(g), em.sigma_g[g], float(em.max_eta_diff[g]))
             for g in a[code == RESTART]:
                 g = int(g)
                 sync_model(g)
@@ -295,12 +277,9 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
                     self._restart_state(theta_0, None)
                     self.fix_params["sigma_epsilon"] = self.sigma_epsilon = 0.95
                 em.restart(g, M[g]["pi"], 0.95, M[g]["tau_beta"])
-            keep = (code == 0) | (code == RESTART)
-            if not keep.all():
-                self._set_active(a[keep])
-            active = a[keep]
-            if on_iteration is not None:
-                on_iteration(i)
+            return self._narrow(a, keeps_going(code))
+
+        run_rounds(em, np.arange(G), sweep, self._model_sums, settle, max_rounds=max_iter, on_iteration=on_iteration)
         em.finish()
         for g in range(G):
             sync_model(g)
@@ -315,7 +294,7 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
             lp = M[self._gindex[c]]["_last_prep"]
             if lp is not None:                                     # var_tau of the chromosome's LAST E-step (sync_host)
                 sigma_epsilon, tau_beta, lam = lp
-                self.var_tau[c] = (self.n_per_snp[c] * (1.0 + lam) / sigma_epsilon) + tau_beta
+                self.var_tau[c] = self._var_tau_of(c, lam, sigma_epsilon, tau_beta)
         self._host_stale = False
         self.zeta = self.compute_zeta()
         self.pi = {c: M[g]["pi"] for g, c in enumerate(groups)}
@@ -323,20 +302,8 @@ class VIPRSMixPerChromosome(PerChromosomeGroups, VIPRSMix):
         self.tau_beta = {c: M[g]["tau_beta"] for g, c in enumerate(groups)}
         self._sigma_g = {c: M[g]["_sigma_g"] for g, c in enumerate(groups)}
         self.history = {c: M[g]["history"] for g, c in enumerate(groups)}
-        self.optim_results = {c: M[g]["optim_result"] for g, c in enumerate(groups)}
-        res = self.optim_result = OptimizeResult()
-        res.nit = max(r.nit for r in self.optim_results.values())
-        res.success = all(r.success for r in self.optim_results.values())
-        res.stop_iteration = True
-        res.fun = float(np.sum([h["ELBO"][-1] for h in self.history.values()]))
-        failed = [c for c in groups if not self.optim_results[c].success]
-        res.message = "All chromosomes converged." if not failed else \
-            "Not converged: chromosome(s) " + ", ".join(str(c) for c in failed)
-        self.update_posterior_moments()
-        self._gather_posterior()
-        for c in failed:
-            logger.warning("\tchromosome %s: %s", c, self.optim_results[c].message)
-        return self
+        return self._publish_results({c: M[g]["optim_result"] for g, c in enumerate(groups)},
+                                     float(np.sum([h["ELBO"][-1] for h in self.history.values()])))
 
     # ---- summaries: one value per chromosome --------------------------------------------------------------------------------
     def get_null_pi(self, chrom=None):

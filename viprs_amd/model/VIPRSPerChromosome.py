@@ -30,70 +30,11 @@ import logging
 import numpy as np
 
 from ..parallel import broadcast_from_root
-from ..utils.optim import OptimizeResult
-from ._lockstep import RESTART, LockstepEM
-from .VIPRS import VIPRS, _is_numeric
+from ._lockstep import RESTART, LockstepEM, keeps_going, run_rounds
+from ._per_chromosome import PerChromosomeGroups
+from .VIPRS import VIPRS
 
 logger = logging.getLogger(__name__)
-
-
-class PerChromosomeGroups:
-    """What the per-chromosome batches of every model family share (mixed in FRONT of the model class): the chromosomes as
-    SNP groups of the one device state, their sample sizes / SNP counts / lambda_min, the convergence mask over LD blocks, the
-    per-chromosome result tables."""
-
-    _always_merge = True
-
-    def __init__(self, gdl, lambda_min=None, **kwargs):
-        """Arguments of the model class; ``lambda_min='infer'`` gives every chromosome the value of ITS LD matrix (each of the
-        reference's per-chromosome models infers its own, VIPRS.py:186-191); ``lambda_min='compute'`` the value computed on
-        the device from ITS LD blocks."""
-        compute = isinstance(lambda_min, str) and lambda_min == "compute"
-        infer = lambda_min is not None and not _is_numeric(lambda_min) and not compute
-        super().__init__(gdl, lambda_min=None if infer else lambda_min, **kwargs)
-        self.groups = sorted(self._all_shapes)                     # one model per chromosome of the data loader
-        self._gindex = {c: g for g, c in enumerate(self.groups)}
-        ss = gdl.sumstats_table
-        self._n_group = np.array([float(np.max(ss[c].n_per_snp)) for c in self.groups])      # BayesPRSModel.py:75
-        self._m_group = np.array([int(self._all_shapes[c]) for c in self.groups], dtype=np.int64)
-        if infer:
-            ld = gdl.get_ld_matrices()
-            self._lambda_group = [ld[c].get_lambda_min(min_max_ratio=1e-3) for c in self.groups]
-        elif compute:
-            self._lambda_group = [self.lambda_min_computed[c] for c in self.groups]
-            self.lambda_min = 0.0                                  # (as with 'infer': the groups carry the values)
-        else:
-            self._lambda_group = [self.lambda_min] * len(self.groups)
-        self.optim_results = {}
-        self._em = None
-        if self._e_step_fn is None:
-            if not self._merged:
-                raise NotImplementedError(type(self).__name__ + " runs on the device-resident one-plan layout "
-                                          "(device_resident=True, merge_chromosomes=True)")
-            ds, plan = self._dstate["*"], self._plans["*"]
-            sizes = [int(self.shapes.get(c, 0)) for c in self.groups]
-            self._group_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            ds.set_groups(self._group_start)
-            starts, _ = plan.blocks()
-            # (`right`: a chromosome without local SNPs shares its start with the next one, which owns the block)
-            self._block_group = np.searchsorted(self._group_start, starts[:-1], side="right") - 1
-            self._active_mask = None
-
-    def _set_active(self, active_groups):
-        """The chromosomes whose models still iterate: the LD blocks of the others leave the sweep."""
-        if self._e_step_fn is not None:
-            return
-        flags = np.zeros(len(self.groups), dtype=bool)
-        flags[active_groups] = True
-        mask = flags[self._block_group]
-        self._plans["*"].set_active_blocks(None if mask.all() else mask)
-
-    def get_heritability(self):
-        return {c: self._sigma_g[c] / (self._sigma_g[c] + self.sigma_epsilon[c]) for c in self.groups}
-
-    def to_history_table(self):
-        import pandas as pd
-        return pd.concat([pd.DataFrame(h).assign(Chromosome=c) for c, h in self.history.items()])
 
 
 class VIPRSPerChromosome(PerChromosomeGroups, VIPRS):
@@ -115,10 +56,7 @@ class VIPRSPerChromosome(PerChromosomeGroups, VIPRS):
 
     def _theta_for(self, c, theta_0):
         """(pi, sigma_epsilon, tau_beta) of chromosome c's model as `VIPRS.initialize_theta` would leave them."""
-        t0 = theta_0
-        if isinstance(theta_0, dict) and theta_0 and all(k in self._gindex for k in theta_0):
-            t0 = theta_0.get(c)                                    # {chromosome: theta_0}
-        th = self._merge_theta(dict(t0) if t0 else None)
+        th = self._merge_theta(self._theta0_for(c, theta_0))
         return self._theta_values(th, int(self._m_group[self._gindex[c]]), lambda: self._h2_start(c))
 
     def _cast_group_theta(self, raw):
@@ -174,19 +112,14 @@ class VIPRSPerChromosome(PerChromosomeGroups, VIPRS):
     def _group_sums(self, a, em, on_host=False):
         """(len(a), 11) rows in the layout of `viprs_state_sums`, [0] = mean of gamma over the chromosome, all ranks."""
         if self._e_step_fn is not None or on_host:
-            s = self._host_group_sums(a)
-            reduced = False
+            s, reduced = self._host_group_sums(a), False
         else:
             ds = self._dstate["*"]
             ds.sums_groups_begin(a, em.lam1[a])
             s = ds.sums_groups_end()
             s[:, 0] /= self._m_group[a]
             reduced = self._device_reduce
-        if self.comm.world_size > 1 and not reduced:
-            tot = self.comm.allreduce_sum(np.ascontiguousarray(s[:, :10]).ravel()).reshape(-1, 10)
-            mx = self.comm.allreduce_max(np.ascontiguousarray(s[:, 10]))
-            s = np.column_stack([tot, mx])
-        return s
+        return self._all_rank_sums(s, reduced)
 
     # ---- the fit -----------------------------------------------------------------------------------------------------
     def fit(self, max_iter=1000, theta_0=None, param_0=None, continued=False, disable_pbar=True, min_iter=3,
@@ -221,48 +154,27 @@ class VIPRSPerChromosome(PerChromosomeGroups, VIPRS):
         self._sums, self._sums_valid = None, False
         self._track(all_groups, em)
 
-        active = all_groups
-        for i in range(1, max_iter + 1):
-            if active.size == 0:
-                break
-            a = active
-            em.mark_e_step(a)
-            self._sweep(a, em)
-            code = em.update(a, self._group_sums(a, em), i)
-            for g in a:
-                self.history[self.groups[g]]["ELBO"].append(float(em.elbos[g]))
-            self._track(a, em)
+        def settle(a, code, i):
+            self._track(a, em, elbo=True)
             for g in a[code == RESTART]:
                 self._restart_group(int(g), em, theta_0, i)
-            keep = (code == 0) | (code == RESTART)
-            if not keep.all():
-                self._set_active(a[keep])
-            active = a[keep]
-            if on_iteration is not None:
-                on_iteration(i)
+            return self._narrow(a, keeps_going(code))
+
+        run_rounds(em, all_groups, lambda a: self._sweep(a, em), lambda a: self._group_sums(a, em), settle,
+                   max_rounds=max_iter, on_iteration=on_iteration)
         em.finish()
         self._set_active(all_groups)
         self.fix_params = base_fixed
         return self._publish(em)
 
-    def _track(self, a, em):
-        for t in self.tracked_params:
-            for g in a:
-                h, (pi, sig, tau) = self.history[self.groups[g]], em.theta(g)
-                if t == "pi":
-                    h["pi"].append(pi)
-                elif t == "heritability":
-                    h["heritability"].append(em.sigma_g[g] / (em.sigma_g[g] + sig))
-                elif t == "sigma_epsilon":
-                    h["sigma_epsilon"].append(sig)
-                elif t == "tau_beta":
-                    h["tau_beta"].append(tau)
-                elif t == "sigma_g":
-                    h["sigma_g"].append(em.sigma_g[g])
-                elif t == "max_eta_diff":
-                    h["max_eta_diff"].append(em.max_eta_diff[g])
-                elif callable(t):
-                    raise NotImplementedError("callable tracked_params are not supported by the per-chromosome fit")
+    def _track(self, a, em, elbo=False):
+        """The history of models `a` after an iteration (`elbo`: its ELBO first; the initial one is `VIPRS.elbo`'s)."""
+        for g in a:
+            h = self.history[self.groups[g]]
+            if elbo:
+                h["ELBO"].append(float(em.elbos[g]))
+            if self.tracked_params:
+                self._append_tracked(h, em.theta(g), em.sigma_g[g], em.max_eta_diff[g])
 
     def _restart_group(self, g, em, theta_0, i):
         """Negative MSE with a free sigma_epsilon: that chromosome's model starts again with sigma_epsilon = 0.95
@@ -285,8 +197,7 @@ class VIPRSPerChromosome(PerChromosomeGroups, VIPRS):
             self._pull_state()
         for c in self.chromosomes:
             g = self._gindex[c]
-            lam = self._T.type(self._lambda_group[g])
-            self.var_tau[c] = (self.n_per_snp[c] * (1.0 + lam) / em.sig_e[g]) + em.tau_e[g]
+            self.var_tau[c] = self._var_tau_of(c, self._T.type(self._lambda_group[g]), em.sig_e[g], em.tau_e[g])
             self._log_var_tau[c] = np.log(self.var_tau[c])
         self._host_stale = False
         self.zeta = self.compute_zeta()
@@ -294,20 +205,7 @@ class VIPRSPerChromosome(PerChromosomeGroups, VIPRS):
         self.sigma_epsilon = {c: em.theta(g)[1] for g, c in enumerate(groups)}
         self.tau_beta = {c: em.theta(g)[2] for g, c in enumerate(groups)}
         self._sigma_g = {c: em.sigma_g[g] for g, c in enumerate(groups)}
-        self.optim_results = {c: em.results[g] for g, c in enumerate(groups)}
-        res = self.optim_result = OptimizeResult()
-        res.nit = max(r.nit for r in em.results)
-        res.success = all(r.success for r in em.results)
-        res.stop_iteration = True
-        res.fun = float(np.sum(em.elbos))
-        failed = [str(c) for c in groups if not self.optim_results[c].success]
-        res.message = "All chromosomes converged." if not failed else "Not converged: chromosome(s) " + ", ".join(failed)
-        self.update_posterior_moments()
-        self._gather_posterior()
-        for c in groups:
-            if not self.optim_results[c].success:
-                logger.warning("\tchromosome %s: %s", c, self.optim_results[c].message)
-        return self
+        return self._publish_results({c: em.results[g] for g, c in enumerate(groups)}, float(np.sum(em.elbos)))
 
     # ---- summaries: one value per chromosome ------------------------------------------------------------------------------
     def elbo(self, sum_axis=None):

@@ -13,8 +13,7 @@ is made per model.  `VIPRSMixPerChromosome(host="scalar")` runs the serial code 
 """
 import numpy as np
 
-from ..utils.optim import OptimizeResult
-from ._lockstep import MAX_ITER_MESSAGE, MESSAGES, RESTART, SUCCESS, _close, _is32, in_dtype
+from ._lockstep import LockstepRules, _is32, in_dtype
 
 f32, f64 = np.float32, np.float64
 
@@ -23,7 +22,7 @@ def _vec_is32(v):
     return isinstance(v, np.ndarray) and v.dtype == np.float32
 
 
-class LockstepMixEM:
+class LockstepMixEM(LockstepRules):
     """Hyper-parameters, ELBO history and stopping state of G K-component models as arrays.
 
     :param T: the state precision (np.dtype).
@@ -35,7 +34,9 @@ class LockstepMixEM:
 
     def __init__(self, T, th, d, n_snps, n, min_iter=3, f_abs_tol=1e-6, x_abs_tol=1e-6, patience=10):
         G = len(th)
-        self.T, self.G, self.K = np.dtype(T), G, len(d)
+        # (no model is ever `fresh`; a negative MSE with a free sigma_epsilon always reports `RESTART`)
+        super().__init__(G, min_iter, f_abs_tol, x_abs_tol, patience, restart_free_sigma=True)
+        self.T, self.K = np.dtype(T), len(d)
         self.d = np.asarray(d)
         self.d64 = self.d.astype(f64)
         self.pi = np.array([np.asarray(p["pi"]) for p in th], dtype=self.T).reshape(G, self.K)
@@ -60,14 +61,7 @@ class LockstepMixEM:
         self.n_snps = np.asarray(n_snps, dtype=np.int64)
         self._n_snps_T = self.n_snps.astype(self.T)                             # (a T scalar times a Python int is a T product)
         self.n = np.asarray(n, dtype=f64)
-        self.min_iter, self.f_abs_tol, self.x_abs_tol, self.patience = min_iter, f_abs_tol, x_abs_tol, patience
-        self.results = [OptimizeResult() for _ in range(G)]
         self.sigma_g = np.zeros(G)
-        self.prev_elbo = np.full(G, -np.inf)
-        self.prev_sigma_g = np.zeros(G)
-        self.plateau_n, self.dropping_n = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
-        self.elbos = np.zeros(G)
-        self.max_eta_diff = np.zeros(G)
 
     # ---- E-step inputs ------------------------------------------------------------------------------------------------------
     def prep_rows(self, a):
@@ -94,8 +88,9 @@ class LockstepMixEM:
 
     # ---- M-step, ELBO, stopping rules ---------------------------------------------------------------------------------------
     def update(self, a, s, i):
-        """Models `a` on iteration `i` from their sums `s` ((len(a), 7 + 6 K), the layout of `viprs_state_sums_mixture_end`).
-        Returns the stop code per model (0 = keeps going, `RESTART` = negative MSE with a free sigma_epsilon)."""
+        """M-step, ELBO and stopping rules of models `a` on iteration `i` from their sums `s` ((len(a), 7 + 6 K), the layout
+        of `viprs_state_sums_mixture_end`).  Returns the stop code per model (0 = keeps going, `RESTART` = negative MSE with
+        a free sigma_epsilon)."""
         T, K = self.T, self.K
         kv = [s[:, 6 + j * K: 6 + (j + 1) * K] for j in range(6)]
         fx_sig = self.fx_sig[a]
@@ -138,34 +133,9 @@ class LockstepMixEM:
             e = e - (s[:, 4] - np.log(null_pi).astype(f64) * s[:, 5])
             e = e + 0.5 * ((in_dtype(ta, tau32, lambda v: 1.0 + np.log(v))) * kv[3] - kv[4]).sum(axis=1)
             e = e - 0.5 * (ta * kv[5]).sum(axis=1)
-        self.elbos[a] = e
-        self.max_eta_diff[a] = s[:, -1]
-        mse = 1.0 - 2.0 * s[:, 2] + (sg - s[:, 0] + s[:, 3])                    # VIPRSMix.mse
-        with np.errstate(all="ignore"):
             h2 = sg / (sg + sa)
-        # ---- VIPRS.fit stopping rules (VIPRS.py:1003-1080), first match wins ----
-        min_iter, x_abs_tol, f_abs_tol = self.min_iter, self.x_abs_tol, self.f_abs_tol
-        prev_e, late = self.prev_elbo[a], i > min_iter
-        pl = late & _close(sg, self.prev_sigma_g[a], x_abs_tol) & (s[:, -1] < x_abs_tol * 10)
-        dr = (e < prev_e) & ~_close(e, prev_e, 1e3 * f_abs_tol, 1e-4)
-        pn = self.plateau_n[a] = np.where(pl, self.plateau_n[a] + 1, 0)
-        dn = self.dropping_n[a] = np.where(dr, self.dropping_n[a] + 1, 0)
-        code = np.zeros(len(a), dtype=np.int64)
-        for c, cond in ((8, dn > self.patience), (7, pn > self.patience), (6, late & (s[:, -1] < x_abs_tol)),
-                        (5, late & _close(prev_e, e, f_abs_tol)), (4, (h2 > 1.0) | (h2 < 0.0)), (3, sa < 0.0),
-                        (2, ~np.isfinite(e)), (1, mse < 0.0)):                  # (applied last = matched first)
-            code = np.where(cond, c, code)
-        code = np.where((code == 1) & ~fx_sig, RESTART, code)
-        for k, g in enumerate(a):
-            c = int(code[k])
-            if c == 0:
-                self.results[g].update(float(e[k]))
-            elif c != RESTART:
-                msg = MESSAGES[c].format(float(mse[k])) if c == 1 else MESSAGES[c]
-                self.results[g].update(float(e[k]), stop_iteration=True, success=SUCCESS[c], message=msg)
-        keep = code != RESTART              # (VIPRS.fit returns from the iteration before the bookkeeping on a restart)
-        self.prev_elbo[a[keep]], self.prev_sigma_g[a[keep]] = e[keep], sg[keep]
-        return code
+        mse = 1.0 - 2.0 * s[:, 2] + (sg - s[:, 0] + s[:, 3])                    # VIPRSMix.mse
+        return self.stop_codes(a, e, sg, sa, h2, mse, s[:, -1], i, fx_sig)
 
     def restart(self, g, pi, sigma_epsilon, tau_beta):
         """Model g starts again from (pi, tau_beta) with sigma_epsilon FIXED at the given value (VIPRS.py:1030-1036)."""
@@ -173,12 +143,6 @@ class LockstepMixEM:
         self.tau[g], self.tau_is32[g] = np.asarray(tau_beta, dtype=f64), _vec_is32(np.asarray(tau_beta))
         self.sig[g], self.sig_is32[g], self.sig_is_py[g] = sigma_epsilon, _is32(sigma_epsilon), type(sigma_epsilon) is float
         self.fx_sig[g] = True
-
-    def finish(self):
-        for g in range(self.G):
-            if not self.results[g].stop_iteration:
-                self.results[g].update(self.elbos[g], stop_iteration=True, success=False, increment=False,
-                                       message=MAX_ITER_MESSAGE)
 
     def theta(self, g):
         """(pi, sigma_epsilon, tau_beta) of model g in the serial fit's dtypes."""

@@ -21,7 +21,7 @@ import numpy as np
 import pandas as pd
 
 from ..VIPRS import VIPRS
-from .._lockstep import LockstepEM
+from .._lockstep import LockstepEM, run_rounds
 
 
 class VIPRSGrid(VIPRS):
@@ -259,19 +259,14 @@ class VIPRSGrid(VIPRS):
         for st in states.values():               # initial ELBO needs var_tau of the initial hyper-parameters
             st.prep_columns(em.prep_rows(active))
 
-        for i in range(1, max_iter + 1):
-            if active.size == 0:
-                break
-            a = active
-            em.mark_e_step(a)                                                   # what var_tau is built from
+        def sweep(a):
             rows = em.prep_rows(a)
             for st in states.values():               # one prep launch, one sweep and one reduction per plan
                 st.prep_columns(rows)
                 st.e_step(self.dequantize_scale, active_model_idx=a, sync=False)
-            code = em.update(a, all_sums(a), i)
-            active = a[code == 0]
-            if on_iteration is not None:
-                on_iteration(i)
+
+        run_rounds(em, active, sweep, all_sums, lambda a, code, i: a[code == 0], max_rounds=max_iter,
+                   on_iteration=on_iteration)
         em.finish()
         self._lockstep = (em, states, all_sums)        # (measurement hook: bench.py takes an iteration apart phase by phase)
         results, sigma_g, elbos = em.results, em.sigma_g, em.elbos

@@ -30,7 +30,7 @@ WHOLE pathwise trajectory (its initial ELBO, then one entry per iteration of eve
 import numpy as np
 
 from ...utils.optim import OptimizeResult
-from .._lockstep import RESTART, LockstepEM
+from .._lockstep import RESTART, LockstepEM, run_rounds
 from ..VIPRS import VIPRS
 from ..VIPRSPerChromosome import VIPRSPerChromosome
 from .VIPRSGridPerChromosome import GridPerChromosomeMixin
@@ -134,16 +134,9 @@ class VIPRSGridPathwisePerChromosome(GridPerChromosomeMixin, VIPRSPerChromosome)
         n_point = np.zeros(C, dtype=np.int64)           # iterations of the current point (max_iter bounds each point)
         rec = {c: dict(var_tau=np.empty((int(self._m_group[g]), G), dtype=T), theta=[None] * G, sigma_g=np.zeros(G),
                        elbo=np.empty(G, dtype=T), results=[None] * G) for g, c in enumerate(self.groups)}
-        active, rnd = all_groups, 0
-        while active.size:
-            a = active
-            rnd += 1
-            em.mark_e_step(a)
-            self._sweep(a, em)
-            code = em.update(a, self._group_sums(a, em), it[a])
-            for g in a:
-                self.history[self.groups[g]]["ELBO"].append(float(em.elbos[g]))
-            self._track(a, em)
+
+        def settle(a, code, rnd):
+            self._track(a, em, elbo=True)
             for g in a[code == RESTART]:
                 self.fix_params = fixed[g]
                 self._restart_group(int(g), em, theta_0, int(it[g]))
@@ -152,28 +145,28 @@ class VIPRSGridPathwisePerChromosome(GridPerChromosomeMixin, VIPRSPerChromosome)
             n_point[a] += 1
             stopped = (code != 0) & (code != RESTART)
             out = a[stopped | (~stopped & (n_point[a] >= max_iter))]
-            if out.size:
-                em.finish(out)
-                self._commit(store, out, point[out])
-                for g in out:
-                    self._record(rec[self.groups[g]], int(point[g]), int(g), em, lam[g])
-                moving = out[point[out] + 1 < G]
-                for g in moving:
-                    c = self.groups[g]
-                    point[g] += 1
-                    p = points[c][point[g]]
-                    fixed[g].update(p)
-                    if "lambda_min" in p:
-                        lam[g] = T.type(p["lambda_min"])
-                    em.advance(int(g), p)
-                    it[g] = len(self.history[c]["ELBO"]) + 1
-                    n_point[g] = 0
-                done = np.setdiff1d(out, moving)
-                active = np.setdiff1d(a, done)
-                if done.size:
-                    self._set_active(active)
-            if on_iteration is not None:
-                on_iteration(rnd)
+            if not out.size:
+                return a
+            em.finish(out)
+            self._commit(store, out, point[out])
+            for g in out:
+                self._record(rec[self.groups[g]], int(point[g]), int(g), em, lam[g])
+            moving = out[point[out] + 1 < G]
+            for g in moving:
+                c = self.groups[g]
+                point[g] += 1
+                p = points[c][point[g]]
+                fixed[g].update(p)
+                if "lambda_min" in p:
+                    lam[g] = T.type(p["lambda_min"])
+                em.advance(int(g), p)
+                it[g] = len(self.history[c]["ELBO"]) + 1
+                n_point[g] = 0
+            return self._narrow(a, ~np.isin(a, np.setdiff1d(out, moving)))       # (after its last point: out of the sweep)
+
+        # (`max_iter` bounds every grid point, not the run: no bound on the rounds)
+        run_rounds(em, all_groups, lambda a: self._sweep(a, em), lambda a: self._group_sums(a, em), settle,
+                   iteration=lambda a: it[a], on_iteration=on_iteration)
         self._set_active(all_groups)
         self.fix_params = base_fixed
         self._sums, self._sums_valid = None, False
@@ -189,4 +182,4 @@ class VIPRSGridPathwisePerChromosome(GridPerChromosomeMixin, VIPRSPerChromosome)
         r["elbo"][i] = self.history[c]["ELBO"][-1]
         r["theta"][i] = em.theta(g)
         r["sigma_g"][i] = em.sigma_g[g]
-        r["var_tau"][:, i] = (self.n_per_snp[c] * (1.0 + lam) / em.sig_e[g]) + em.tau_e[g]
+        r["var_tau"][:, i] = self._var_tau_of(c, lam, em.sig_e[g], em.tau_e[g])

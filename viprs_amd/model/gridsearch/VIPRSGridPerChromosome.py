@@ -32,9 +32,9 @@ import copy
 
 import numpy as np
 
-from .._lockstep import LockstepEM, f64
+from .._lockstep import LockstepEM, f64, run_rounds
+from .._per_chromosome import PerChromosomeGroups
 from ..VIPRS import VIPRS
-from ..VIPRSPerChromosome import PerChromosomeGroups
 from .VIPRSGrid import VIPRSGrid
 
 _RES = np.finfo(np.float64).resolution
@@ -207,11 +207,9 @@ class VIPRSGridPerChromosome(GridPerChromosomeMixin, PerChromosomeGroups, VIPRSG
         th = []
         for gi, c in enumerate(self.groups):
             m_c = int(self._m_group[gi])
-            t0 = theta_0.get(c) if isinstance(theta_0, dict) and theta_0 and all(k in self._gindex for k in theta_0) \
-                else theta_0
             for params in self.grid_tables[c].to_dict(orient="records"):
                 self.fix_params = {**base_fixed, **params}
-                pi, sig, tau = self._theta_values(self._merge_theta(dict(t0) if t0 else None), m_c)
+                pi, sig, tau = self._theta_values(self._merge_theta(self._theta0_for(c, theta_0)), m_c)
                 lam = T.type(params["lambda_min"]) if "lambda_min" in params else self._lambda_group[gi]
                 th.append(dict(pi=T.type(pi), sigma_epsilon=T.type(sig), tau_beta=tau, lam=lam, fixed=set(self.fix_params)))
         self.fix_params = base_fixed
@@ -314,23 +312,18 @@ class VIPRSGridPerChromosome(GridPerChromosomeMixin, PerChromosomeGroups, VIPRSG
         self._init_state(em)
         self._set_active(np.arange(C))
         self.history = {c: {"ELBO": [[] for _ in range(G)]} for c in self.groups}
-        active = np.arange(C * G)
-        for i in range(1, max_iter + 1):
-            if active.size == 0:
-                break
-            a = active
-            em.mark_e_step(a)
-            self._sweep(a, em)
-            code = em.update(a, self._pair_sums(a, em), i)
+
+        def settle(a, code, i):
             for k in a:
                 self.history[self.groups[k // G]]["ELBO"][k % G].append(float(em.elbos[k]))
             active = a[code == 0]
-            if active.size < a.size:
-                left = np.unique(active // G)
-                if left.size < np.unique(a // G).size:
-                    self._set_active(left)
-            if on_iteration is not None:
-                on_iteration(i)
+            if active.size < a.size:                     # a chromosome whose pairs have all stopped leaves the sweep
+                ga = np.unique(a // G)
+                self._narrow(ga, np.isin(ga, active // G))
+            return active
+
+        run_rounds(em, np.arange(C * G), lambda a: self._sweep(a, em), lambda a: self._pair_sums(a, em), settle,
+                   max_rounds=max_iter, on_iteration=on_iteration)
         em.finish()
         self._set_active(np.arange(C))
         return self._publish_pairs(em, th)
@@ -348,7 +341,7 @@ class VIPRSGridPerChromosome(GridPerChromosomeMixin, PerChromosomeGroups, VIPRSG
             ks = gi * G + np.arange(G)
             vt = np.empty((int(self._m_group[gi]), G), dtype=T)
             for g, k in enumerate(ks):                           # what the LAST E-step of the pair was built from
-                vt[:, g] = (self.n_per_snp[c] * (1.0 + th[k]["lam"]) / em.sig_e[k]) + em.tau_e[k]
+                vt[:, g] = self._var_tau_of(c, th[k]["lam"], em.sig_e[k], em.tau_e[k])
             rec[c] = dict(var_tau=vt, theta=[em.theta(k) for k in ks], sigma_g=em.sigma_g[ks], elbo=em.elbos[ks].astype(T),
                           results=[em.results[k] for k in ks])
         return self._publish_chromosomes(rec)
