@@ -668,6 +668,39 @@ int viprs_genotypes_ld(viprs_genotypes* g, int64_t row0, int64_t row1, const int
                        const double* w /* m */, int out_dtype, void* data_host /* rows [row0,row1) of the store */);
 int viprs_genotypes_last_ld_ms(viprs_genotypes* g, double* ms);
 
+/* ---- per-genotype-class column sums: what an association test (GWAS) of the .bed rows is derived from ---------------------
+ * One generic device operation; every association statistic is derived from it on the host in double
+ * (viprs_amd/genotypes.py, `association`).  magenpy and plink2 compute the reference's GWAS; neither is part of the reference
+ * tree, so nothing here claims parity with them.  The definition below is the contract.
+ * `y_host` is (n, n_cols) row-major double, `sums_host` is (row1 - row0, 3, n_cols) row-major double.
+ * CLASSES.  k = 0: code 0 (two copies of A1);  k = 1: code 2 (one copy);  k = 2: code 3 (no copy).  Code 1 (missing) belongs
+ * to no class.  For SNP j, class k and column c:
+ *   t(i)  = (class(i, j) == k) ? Y[i][c] : +0.0                       for the samples i < n
+ *   s(i)  = (i >> 4) & 63                                             the slot of a sample, VIPRS_CLASS_SUM_SLOTS = 64 slots:
+ *                                                                     the 16 samples of one 32-bit word of the row share a
+ *                                                                     slot, and so do the words w, w + 64, w + 128, ...
+ *   P[s]  = ((+0 + t(i1)) + t(i2)) + ...                              over the samples of slot s in ascending i: plain double
+ *                                                                     additions (__dadd_rn), no fma, nothing reassociated
+ *   butterfly: for d in 32, 16, 8, 4, 2, 1: P[s] <- P[s] + P[s ^ d]   all slots at once
+ * IEEE addition is commutative, so after the last step all 64 values are identical: that value is sums[j - row0][k][c].
+ * The bits of an output depend on row j's genotypes, column c and n only: not on n_cols, on the other columns, on row0 / row1,
+ * on m, on any work-buffer budget or on how the work was tiled; two calls give identical bits.  An accumulator that starts at
+ * +0 never becomes -0 under these additions, so adding +0.0 for a sample of another class is bit-identical to skipping it:
+ * either implementation is allowed.  Y is finite; behaviour on NaN / inf is unspecified.  Slots at or beyond n read as code 1
+ * (viprs_genotypes_upload_rows) and contribute nothing; a row that was never uploaded gives zeros.  n = 0 (zeros) and
+ * row0 == row1 (nothing is written) are legal.
+ * ROUNDING, to first order: |sum - exact| <= (16 ceil(n / 1024) + 6) 2^-53 sum|t|: the longest slot chain -- 16 samples per
+ * word, ceil(n / 1024) words per slot -- plus the six butterfly steps.  Derived, not measured.
+ * n_cols < 1, row0 > row1, a null pointer, rows outside [0, m]: VIPRS_EINVAL before the object is touched or anything is
+ * launched, outputs untouched.  Synchronous, on the object's own stream; the stream is drained before the call's host buffers
+ * go out of scope, on error paths too.  The caller slices the rows so that the output stays bounded.
+ *   viprs_genotypes_last_class_sums_ms   HIP-event time of the kernels of the last class-sums call that launched any */
+#define VIPRS_CLASS_SUM_SLOTS 64
+int viprs_genotypes_class_sums(viprs_genotypes* g, int64_t row0, int64_t row1, int n_cols,
+                               const double* y_host /* n x n_cols, row-major */,
+                               double* sums_host /* (row1-row0) x 3 x n_cols, row-major */);
+int viprs_genotypes_last_class_sums_ms(viprs_genotypes* g, double* ms);
+
 /* ---- measurement support: synthetic LD generated on the device (bench.py, tests) --------------
  * The "longrange" LD blocks of viprs_amd/utils/synthetic.py (the workload of BASELINE.json's configs, SURVEY.md 8d: the
  * reference gets its LD from magenpy stores, VIPRS.py:151-172, none of which exists here) written straight into a plan's

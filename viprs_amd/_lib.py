@@ -145,6 +145,8 @@ _PROTOS = {
     "viprs_genotypes_last_counts_ms": (_i, [_vp, ctypes.POINTER(_d)]),
     "viprs_genotypes_ld": (_i, [_vp, _i64, _i64, _vp, _vp, _i, _vp]),
     "viprs_genotypes_last_ld_ms": (_i, [_vp, ctypes.POINTER(_d)]),
+    "viprs_genotypes_class_sums": (_i, [_vp, _i64, _i64, _i, _vp, _vp]),
+    "viprs_genotypes_last_class_sums_ms": (_i, [_vp, ctypes.POINTER(_d)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -1,6 +1,8 @@
 // C ABI, genotype scoring (include/viprs_hip.h): packed PLINK .bed rows on the device, the per-SNP code counts and the
 // polygenic scores, and the LD matrix of the rows in the compact upper store.  Score kernels: geno_score.h; LD kernels:
-// geno_ld.h; the counts kernel and the kernel that sets the slots beyond n are here.
+// geno_ld.h; per-genotype-class column sums: geno_class_sums.h; the counts kernel and the kernel that sets the slots beyond n
+// are here.
+#include "geno_class_sums.h"
 #include "geno_ld.h"
 #include "geno_score.h"
 
@@ -25,6 +27,8 @@ struct viprs_genotypes {
     DevBuf<double> d_w;
     DevBuf<char> d_ld_out;
     EventBracket time_ld;
+    DevBuf<double> d_class_y, d_class_out;         // class sums: the call's Y in the kernel's layout, the rows of its output
+    EventBracket time_class_sums;
     ~viprs_genotypes() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
@@ -208,6 +212,34 @@ int enqueue_ld(viprs_genotypes* G, int64_t row0, int64_t row1, const int64_t* ri
     return VIPRS_OK;
 }
 
+// Everything `viprs_genotypes_class_sums` puts on the stream: the upload of Y in the kernel's layout, the kernels between the
+// event pair, the download.  Nothing is synchronised here: the caller drains the stream whatever this returns, because the
+// upload reads `y_dev_layout` of the caller's frame
+int enqueue_class_sums(viprs_genotypes* G, int64_t row0, int64_t row1, int n_cols, const std::vector<double>& y_dev_layout,
+                       int64_t n_rounds, double* sums_host) {
+    const size_t out_count = (size_t)(row1 - row0) * 3 * (size_t)n_cols;
+    HIP_TRY(hipMemcpyAsync(G->d_class_y.p, y_dev_layout.data(), y_dev_layout.size() * sizeof(double), hipMemcpyHostToDevice,
+                           G->stream));
+    GenoClassSumsArgs A;
+    A.rows = reinterpret_cast<const uint32_t*>(G->d_rows.p);
+    A.y = G->d_class_y.p;
+    A.out = G->d_class_out.p;
+    A.n_words = G->stride / 4;
+    A.n_rounds = n_rounds;
+    A.row0 = row0;
+    A.row1 = row1;
+    A.n_cols = n_cols;
+    A.col0 = 0;
+    int rc = G->time_class_sums.start(G->stream);
+    if (rc != VIPRS_OK) return rc;
+    rc = launch_geno_class_sums(G->stream, A);
+    if (rc != VIPRS_OK) return rc;
+    rc = G->time_class_sums.stop(G->stream);
+    if (rc != VIPRS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(sums_host, G->d_class_out.p, out_count * sizeof(double), hipMemcpyDeviceToHost, G->stream));
+    return VIPRS_OK;
+}
+
 }  // namespace
 }  // namespace viprs
 
@@ -373,6 +405,47 @@ int viprs_genotypes_ld(viprs_genotypes* G, int64_t row0, int64_t row1, const int
     if (rc != VIPRS_OK) return rc;
     HIP_TRY(drained);
     return VIPRS_OK;
+}
+
+int viprs_genotypes_class_sums(viprs_genotypes* G, int64_t row0, int64_t row1, int n_cols, const double* y_host,
+                               double* sums_host) {
+    // every argument check comes before the object is touched
+    if (n_cols < 1) return fail(VIPRS_EINVAL, "n_cols must be at least 1");
+    if (row0 > row1) return fail(VIPRS_EINVAL, "row0 must not exceed row1");
+    if (!y_host) return fail(VIPRS_EINVAL, "null Y");
+    if (!sums_host) return fail(VIPRS_EINVAL, "null host buffer");
+    if (!G) return fail(VIPRS_EINVAL, "null genotypes");
+    if (row0 < 0 || row1 > G->m) return fail(VIPRS_EINVAL, "rows out of range");
+    if (row0 == row1) return VIPRS_OK;
+    const size_t out_count = (size_t)(row1 - row0) * 3 * (size_t)n_cols;
+    if (G->n == 0) {
+        std::memset(sums_host, 0, out_count * sizeof(double));
+        return VIPRS_OK;
+    }
+    // Y as the kernel reads it: [column][round t][sample-in-word q][lane l], sample i = 1024 t + 16 l + q; zeros beyond n
+    const int64_t n_words = G->stride / 4;
+    const int64_t n_rounds = (n_words + kClassSumSlots - 1) / kClassSumSlots;
+    std::vector<double> y((size_t)n_cols * (size_t)n_rounds * 1024, 0.0);
+    for (int64_t i = 0; i < G->n; ++i) {
+        const size_t at = (size_t)(i >> 10) * 1024 + (size_t)(i & 15) * 64 + (size_t)((i >> 4) & 63);
+        for (int c = 0; c < n_cols; ++c) y[(size_t)c * (size_t)n_rounds * 1024 + at] = y_host[(size_t)i * (size_t)n_cols + c];
+    }
+    HIP_TRY(hipSetDevice(G->device));
+    // (a failed allocation leaves its buffer empty, dev_buf.h: the next call allocates again)
+    if (G->d_class_y.reserve(y.size()) != hipSuccess) return fail(VIPRS_ENOMEM, "no device memory for Y");
+    if (G->d_class_out.reserve(out_count) != hipSuccess)
+        return fail(VIPRS_ENOMEM, "no device memory for the class sums: give a smaller row range");
+    const int rc = enqueue_class_sums(G, row0, row1, n_cols, y, n_rounds, sums_host);
+    // on the error paths too: the upload reads `y` until the stream is drained
+    const hipError_t drained = hipStreamSynchronize(G->stream);
+    if (rc != VIPRS_OK) return rc;
+    HIP_TRY(drained);
+    return VIPRS_OK;
+}
+
+int viprs_genotypes_last_class_sums_ms(viprs_genotypes* G, double* ms) {
+    if (!G || !ms) return fail(VIPRS_EINVAL, "null argument");
+    return G->time_class_sums.elapsed(G->device, ms, "no timed class-sums call yet");
 }
 
 int viprs_genotypes_last_ld_ms(viprs_genotypes* G, double* ms) {

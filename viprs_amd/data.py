@@ -211,6 +211,35 @@ class ArrayDataLoader:
             self.ld_estimator[c] = est[0]
         return self.ld
 
+    # ---- genotypes: the loader's own summary statistics (magenpy's ``GWADataLoader.perform_gwas``) -----------------------
+    def perform_gwas(self, phenotype=None, keep=None):
+        """Summary statistics of every chromosome that has genotypes, from the genotypes and the phenotype (`phenotype`,
+        ``(n_samples,)``, or the loader's own; NaN = unknown; a .bed prefix brings the .fam's): the per-SNP linear regression
+        of `viprs_amd.genotypes._Genotypes.association` over the samples of `keep` (None: all).
+        ``self.sumstats_table[c]`` becomes ``SumstatsArrays(std_beta=R, n_per_snp=N, chisq=Z**2)``, ``self.gwas_table[c]`` keeps
+        the full table (N, BETA, SE, Z, R, A1_FREQ), ``self.shapes`` and ``self.n`` follow.  The effect allele is the .bed's
+        A1.  Returns ``self.sumstats_table``."""
+        if not self.genotype:
+            raise ValueError("this loader holds no genotypes: perform_gwas() needs them.  Remedy: ArrayDataLoader(..., "
+                             "genotype={chromosome: .bed prefix | (packed_rows, n) | DeviceGenotypes}).")
+        opened = {c: self._open_genotypes(c) for c in sorted(self.genotype)}    # (a prefix may bring the phenotype)
+        y = self.phenotype if phenotype is None else phenotype
+        if y is None:
+            raise ValueError("this loader has no phenotype: perform_gwas() needs one.  Remedy: perform_gwas(phenotype="
+                             "<(n_samples,) array>), ArrayDataLoader(..., phenotype=...), or a .fam file with a phenotype "
+                             "column.")
+        y = np.asarray(y, dtype=np.float64)
+        self.gwas_table = dict(getattr(self, "gwas_table", {}))
+        for c, g in opened.items():
+            if y.shape != (g.n,):
+                raise ValueError(f"chromosome {c}: a phenotype of shape {y.shape} against {g.n} genotyped samples")
+            table = g.association(y, keep=keep)
+            self.gwas_table[c] = table
+            self.sumstats_table[c] = SumstatsArrays(std_beta=table["R"], n_per_snp=table["N"], chisq=table["Z"] ** 2)
+            self.shapes[c] = int(g.m)
+        self.n = float(max(s.n_per_snp.max() if s.n_per_snp.size else 0.0 for s in self.sumstats_table.values()))
+        return self.sumstats_table
+
     def write_ld_stores(self, ld_dir, **kw):
         """The LD of `compute_ld` as one zarr store per chromosome under `ld_dir` (``chr_<c>``), with the attributes
         `ZarrLDMatrix` reads back: ``{chromosome: path}``.  `kw` goes to `viprs_amd.io.zarr_ld.write_ld_store`."""

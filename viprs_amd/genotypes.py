@@ -16,6 +16,9 @@ dose table, built here on the host in double from the exact counts and rounded o
 * ``HostGenotypes``      the same surface over `score_host` (what a loader uses when no device is visible);
 * ``ld_host``            the LD matrix of the rows from the definition (`viprs_genotypes_ld`), ``ld_windows`` the windows of
                          an estimator; both classes have ``ld()``;
+* ``class_sums_host``    per SNP and genotype class (two / one / no copy of A1) the sums of the columns of ``Y`` over the
+                         samples of the class (`viprs_genotypes_class_sums`); both classes have ``class_sums()`` and, built on
+                         it and the counts alone, ``association()``: the per-SNP linear regression of a GWAS;
 * ``open_genotypes``     a loader's genotype entry -- one of the two above, ``(packed_rows, n)`` or a .bed prefix -- opened;
 * ``model_predict``      ``predict()`` of the model classes.
 """
@@ -259,13 +262,118 @@ def ld_host(packed_rows, n, right_end, dtype=np.float32):
     return ip, data
 
 
+# ---- per-genotype-class column sums and the association test (include/viprs_hip.h, viprs_genotypes_class_sums) ------------
+CLASS_SUM_SLOTS = 64                     # VIPRS_CLASS_SUM_SLOTS: part of the definition of the device sum
+CLASS_CODES = (0, 2, 3)                  # the .bed code of class k = 0, 1, 2: two copies of A1, one, none
+ASSOCIATION_FIELDS = ("N", "BETA", "SE", "Z", "R", "A1_FREQ")
+
+
+def _check_columns(Y, n):
+    """`Y` of `class_sums` as C-contiguous float64 (n, n_cols) -> (Y2, whether it was (n,))."""
+    Y = np.asarray(Y)
+    if Y.ndim not in (1, 2) or Y.shape[0] != n or (Y.ndim == 2 and Y.shape[1] < 1):
+        raise ValueError(f"Y: ({n},) or ({n}, n_cols), got {Y.shape}")
+    Y2 = np.ascontiguousarray(Y.reshape(n, Y.shape[1] if Y.ndim == 2 else 1), dtype=np.float64)
+    if not np.all(np.isfinite(Y2)):
+        raise ValueError("Y holds NaN or inf: class_sums needs finite values (`association` takes NaN as an unknown "
+                         "phenotype and leaves those samples out)")
+    return Y2, Y.ndim == 1
+
+
+def class_sums_host(packed_rows, n, Y):
+    """``sums[j, k, c] = sum of Y[i, c] over the samples i < n whose code at SNP j is CLASS_CODES[k]`` in float64: ``(m, 3)``
+    for ``(n,)`` values, ``(m, 3, n_cols)`` for ``(n, n_cols)``.  Indicator planes times `Y`, in slabs of rows.  The CPU
+    fallback: within the header's rounding bound of the device's sums, not bit-identical to them."""
+    p, n = _check_rows(packed_rows, n)
+    Y2, flat = _check_columns(Y, n)
+    out = np.zeros((p.shape[0], 3, Y2.shape[1]), dtype=np.float64)
+    for a in range(0, p.shape[0], _HOST_SLAB):
+        codes = unpack_codes(p[a:a + _HOST_SLAB], n)
+        for k, code in enumerate(CLASS_CODES):
+            out[a:a + _HOST_SLAB, k] = (codes == code).astype(np.float64) @ Y2
+    return out[:, :, 0] if flat else out
+
+
 class _Genotypes:
-    """What the two genotype classes share: everything that follows from the counts."""
+    """What the two genotype classes share: everything that follows from the counts and the class sums."""
 
     n = m = 0
 
     def counts(self):
         raise NotImplementedError
+
+    def class_sums(self, Y, max_bytes=1 << 30):
+        """Per SNP and genotype class the column sums of `Y` (``(n,)`` or ``(n, n_cols)``, finite) over the samples of the
+        class: ``(m, 3)`` or ``(m, 3, n_cols)`` float64, classes in the order two copies of A1, one, none; missing genotypes
+        belong to no class.  On the device in the order `include/viprs_hip.h` defines, in row ranges whose output stays
+        within `max_bytes` (a row at least)."""
+        raise NotImplementedError
+
+    def association(self, Y, keep=None):
+        """The linear regression of every phenotype column on every SNP's dose of A1 over the complete pairs -- a GWAS without
+        covariates (residualise the phenotype first) -- from `class_sums` and `counts` alone.  `Y`: ``(n,)`` or ``(n, T)``,
+        NaN = unknown phenotype.  `keep`: None, or an ``(n,)`` / ``(n, T)`` boolean mask of the samples that take part (a
+        training subset; K folds of one trait are K columns of one pass).  Per trait the host centres ``y`` by the mean of its
+        kept, known samples and sums the columns ``[u, y u, (y u)^2]`` (``u`` the 0 / 1 mask; dropped when every sample takes
+        part: the class counts are then the exact `counts`) per genotype class; with ``N_k, Y_k, Q_k`` those sums, in double:
+
+            n = N_0 + N_1 + N_2,  Sx = 2 N_0 + N_1,  Sxx = 4 N_0 + N_1,  Sy = sum Y_k,  Syy = sum Q_k,  Sxy = 2 Y_0 + Y_1
+            cxx = n Sxx - Sx^2,  cyy = n Syy - Sy^2,  cxy = n Sxy - Sx Sy
+
+        -> dict of ``(m,)`` / ``(m, T)`` float64: ``N = n``, ``BETA = cxy / cxx`` (per copy of A1),
+        ``SE = sqrt(max(cxx cyy - cxy^2, 0) / (n - 2)) / cxx``, ``Z = BETA / SE``, ``R = cxy / sqrt(cxx cyy)`` (the Pearson
+        correlation: the standardised effect the models read), ``A1_FREQ = Sx / (2 n)``.  A SNP with ``n < 3``,
+        ``cxx <= 0`` or ``cyy <= 0`` gets ``BETA = SE = Z = R = 0`` and its true ``N``.  No P-value."""
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim not in (1, 2) or Y.shape[0] != self.n or (Y.ndim == 2 and Y.shape[1] < 1):
+            raise ValueError(f"phenotype: ({self.n},) or ({self.n}, T), got {Y.shape}")
+        flat = Y.ndim == 1
+        T = 1 if flat else Y.shape[1]
+        Y2 = Y.reshape(self.n, T)
+        if np.any(np.isinf(Y2)):
+            raise ValueError("the phenotype holds inf (NaN marks an unknown phenotype)")
+        u = np.isfinite(Y2)
+        if keep is not None:
+            k = np.asarray(keep)
+            if k.dtype != np.bool_ or k.shape not in ((self.n,), (self.n, T)):
+                raise ValueError(f"keep: a boolean mask of shape ({self.n},) or ({self.n}, {T}), got {k.dtype} {k.shape}")
+            u = u & (k if k.ndim == 2 else k[:, None])
+        n_u = u.sum(axis=0)
+        mean = np.where(u, Y2, 0.0).sum(axis=0) / np.maximum(n_u, 1)
+        yc = np.where(u, Y2 - mean, 0.0)
+        everyone = u.all(axis=0) if self.n else np.ones(T, dtype=bool)
+        cols, at = [], []
+        for t in range(T):
+            at.append(len(cols))
+            if not everyone[t]:
+                cols.append(u[:, t].astype(np.float64))
+            cols += [yc[:, t], yc[:, t] * yc[:, t]]
+        S = self.class_sums(np.stack(cols, axis=1)) if self.n else np.zeros((self.m, 3, len(cols)))
+        out = {f: np.zeros((self.m, T), dtype=np.float64) for f in ASSOCIATION_FIELDS}
+        exact = self.counts()[:, list(CLASS_CODES)].astype(np.float64) if np.any(everyone) else None
+        for t in range(T):
+            a = at[t]
+            if everyone[t]:
+                Nk = exact
+            else:
+                Nk, a = S[:, :, a], a + 1
+            Yk, Qk = S[:, :, a], S[:, :, a + 1]
+            n = Nk.sum(axis=1)
+            Sx, Sxx = 2.0 * Nk[:, 0] + Nk[:, 1], 4.0 * Nk[:, 0] + Nk[:, 1]
+            Sy, Syy, Sxy = Yk.sum(axis=1), Qk.sum(axis=1), 2.0 * Yk[:, 0] + Yk[:, 1]
+            cxx, cyy, cxy = n * Sxx - Sx * Sx, n * Syy - Sy * Sy, n * Sxy - Sx * Sy
+            live = (n >= 3) & (cxx > 0) & (cyy > 0)
+            sxx, syy, dof = np.where(live, cxx, 1.0), np.where(live, cyy, 1.0), np.where(live, n - 2.0, 1.0)
+            beta = np.where(live, cxy / sxx, 0.0)
+            se = np.where(live, np.sqrt(np.maximum(sxx * syy - cxy * cxy, 0.0) / dof) / sxx, 0.0)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                z = np.where(live, beta / se, 0.0)             # (a perfect fit: SE = 0 and Z = +-inf)
+            out["N"][:, t] = n
+            out["BETA"][:, t], out["SE"][:, t], out["Z"][:, t] = beta, se, z
+            out["R"][:, t] = np.where(live, cxy / np.sqrt(sxx * syy), 0.0)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out["A1_FREQ"][:, t] = np.where(n > 0, Sx / (2.0 * n), np.nan)
+        return {f: (v[:, 0] if flat else v) for f, v in out.items()}
 
     def _right_end(self, window):
         """`window` of `ld`: None (every pair), an estimator of `ld_windows`, or the (m,) right ends themselves."""
@@ -331,6 +439,9 @@ class HostGenotypes(_Genotypes):
 
     def ld(self, window=None, dtype=np.float32, max_bytes=1 << 30):
         return ld_host(self.rows, self.n, self._right_end(window), dtype)
+
+    def class_sums(self, Y, max_bytes=1 << 30):
+        return class_sums_host(self.rows, self.n, Y)
 
     def close(self):
         pass
@@ -424,6 +535,26 @@ class DeviceGenotypes(_Genotypes):
                 self.ld_rows(r0, r1, re, w, data[ip[r0]:ip[r1]])
             r0 = r1
         return ip, data
+
+    def class_sums(self, Y, max_bytes=1 << 30):
+        Y2, flat = _check_columns(Y, self.n)
+        n_cols = Y2.shape[1]
+        out = np.zeros((self.m, 3, n_cols), dtype=np.float64)
+        step = max(1, int(max_bytes) // (3 * n_cols * 8))
+        L = self._L
+        spare = np.zeros(1, dtype=np.float64)          # (an empty array may have no address to hand over)
+        for r0 in range(0, self.m, step):
+            r1 = min(self.m, r0 + step)
+            L.check(L.lib.viprs_genotypes_class_sums(self.handle, r0, r1, n_cols,
+                                                     (Y2 if Y2.size else spare).ctypes.data_as(ctypes.c_void_p),
+                                                     out[r0:r1].ctypes.data_as(ctypes.c_void_p)))
+        return out[:, :, 0] if flat else out
+
+    def last_class_sums_ms(self):
+        """HIP-event time (ms) of the kernels of the last device call of `class_sums` on this object (one row range)."""
+        ms = ctypes.c_double(0.0)
+        self._L.check(self._L.lib.viprs_genotypes_last_class_sums_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
 
     def last_ld_ms(self):
         """HIP-event time (ms) of the kernels of the last device call of `ld` / `ld_rows` on this object."""

@@ -49,10 +49,46 @@ def _validation_r2(prs, y):
     return np.nan_to_num(np.array([r2(y, prs[:, i]) for i in range(prs.shape[1])]), nan=0.0, neginf=0.0, posinf=0.0)
 
 
+def pseudo_validation_std_beta(validation_gdl, model_gdl):
+    """``{chromosome: standardized betas}`` of a validation loader's summary statistics (``sumstats_table[c]
+    .get_snp_pseudo_corr()``, e.g. after ``perform_gwas()``: what the reference's ``pseudo_validate(validation_gdl)`` reads),
+    laid out over the model loader's SNPs.  If both loaders have SNP tables the SNPs are aligned by SNP id (`_align` of
+    `viprs_amd.genotypes`): SNPs the validation loader lacks get 0, exchanged alleles flip the sign -- exact for the
+    correlation with ``2 - x`` -- and any other allele pair gets 0.  Without tables the SNP counts must agree."""
+    from ...genotypes import _align
+    val_tables, model_tables = getattr(validation_gdl, "snp_table", None), getattr(model_gdl, "snp_table", None)
+    out = {}
+    for c in sorted(validation_gdl.sumstats_table):
+        r = np.asarray(validation_gdl.sumstats_table[c].get_snp_pseudo_corr(), dtype=np.float64)
+        if val_tables and model_tables and c in val_tables and c in model_tables:
+            # (the validation statistics laid out over the model's SNPs: the model's table is the target of the alignment)
+            r, swapped = _align(val_tables[c], model_tables[c], r, c)
+            r = np.where(swapped, -r, r)
+        elif c in getattr(model_gdl, "shapes", {}) and model_gdl.shapes[c] != r.shape[0]:
+            raise ValueError(f"chromosome {c}: {r.shape[0]} SNPs in the validation loader against {model_gdl.shapes[c]} of "
+                             "the model (give both loaders SNP tables to have them aligned by SNP id)")
+        out[c] = r
+    return out
+
+
+def _validation_std_beta(m, validation_gdl):
+    """The standardized betas of the pseudo_validation criterion: a ``{chromosome: std_beta}`` dict, an object with that dict
+    as ``.std_beta``, a loader with summary statistics (`pseudo_validation_std_beta`), else the model's own."""
+    vb = validation_gdl if isinstance(validation_gdl, dict) else getattr(validation_gdl, "std_beta", None)
+    if vb is None and getattr(validation_gdl, "sumstats_table", None):
+        vb = pseudo_validation_std_beta(validation_gdl, m.gdl)
+    if vb is None:
+        vb = getattr(m, "validation_std_beta", None)
+    if vb is None:
+        raise ValueError("Validation GWADataLoader or standardized betas from a validation set must be "
+                         "initialized for the pseudo_validation criterion.")
+    return vb
+
+
 def select_best_model(viprs_grid_model, validation_gdl=None, criterion="ELBO", validation_ld=None):
     """grid_utils.py:8-100.  `pseudo_validation`: the model with the highest summary-statistics pseudo-R^2 on
     held-out standardized betas -- `validation_gdl` may be a `{chromosome: std_beta}` dict (or an object with
-    that dict as `.std_beta`); otherwise `viprs_grid_model.validation_std_beta` is used.  `validation`: the model with the
+    that dict as `.std_beta`), or a loader with summary statistics (``perform_gwas()``; `pseudo_validation_std_beta`); otherwise `viprs_grid_model.validation_std_beta` is used.  `validation`: the model with the
     highest R^2 of its polygenic score on `validation_gdl`'s genotypes against `validation_gdl.phenotype`
     (``validation_result["Validation_R2"]``; non-finite values count as 0).  `validation_ld` (a
     `{chromosome: LDPlan}` dict, or of `(left_bound, indptr, data, low_memory)` tuples) scores the models against the LD of
@@ -71,12 +107,7 @@ def select_best_model(viprs_grid_model, validation_gdl=None, criterion="ELBO", v
         score = _validation_r2(m.predict(test_gdl=validation_gdl), y)
         m.validation_result["Validation_R2"] = score
     else:
-        vb = validation_gdl if isinstance(validation_gdl, dict) else getattr(validation_gdl, "std_beta", None)
-        if vb is None:
-            vb = getattr(m, "validation_std_beta", None)
-        if vb is None:
-            raise ValueError("Validation GWADataLoader or standardized betas from a validation set must be "
-                             "initialized for the pseudo_validation criterion.")
+        vb = _validation_std_beta(m, validation_gdl)
         score = np.nan_to_num(np.asarray(m.pseudo_validate(vb) if validation_ld is None else
                                          m.pseudo_validate(vb, validation_ld=validation_ld), dtype=np.float64), nan=0.0, neginf=0.0, posinf=0.0)
         m.validation_result["Pseudo_Validation_R2"] = score
@@ -166,7 +197,7 @@ def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO
         # every chromosome's grid is ranked by the score of THAT chromosome's SNPs alone
         y = _validation_phenotype(validation_gdl)
         prs = m.predict(test_gdl=validation_gdl, per_chromosome=True)
-    best = {}
+    best, vb = {}, None
     for c in m.groups:
         ok = np.array([r.valid_optim_result for r in m.optim_results[c]])
         if np.sum(ok) < 2:
@@ -179,12 +210,8 @@ def select_best_model_per_chromosome(model, validation_gdl=None, criterion="ELBO
             score = _validation_r2(prs[c], y)
             m.validation_result[c]["Validation_R2"] = score
         else:
-            vb = validation_gdl if isinstance(validation_gdl, dict) else getattr(validation_gdl, "std_beta", None)
-            if vb is None:
-                vb = getattr(m, "validation_std_beta", None)
-            if vb is None:
-                raise ValueError("Validation GWADataLoader or standardized betas from a validation set must be "
-                                 "initialized for the pseudo_validation criterion.")
+            if vb is None:                                     # (a loader's statistics are laid out once)
+                vb = _validation_std_beta(m, validation_gdl)
             score = np.nan_to_num(np.asarray(m.pseudo_validate(vb, chrom=c) if validation_ld is None else
                                              m.pseudo_validate(vb, chrom=c, validation_ld=validation_ld), dtype=np.float64), nan=0.0, neginf=0.0, posinf=0.0)
             m.validation_result[c]["Pseudo_Validation_R2"] = score
