@@ -396,3 +396,20 @@ def test_annotate_ld_scores(gpu):
     A[::2, 1] = 0.0
     strat = ldsc.ld_scores(gdl.ld[c], annotation=A, dequantize_on_the_fly=True)[None]
     assert strat.shape == A.shape and np.array_equal(strat[:, 0], got[c]) and np.any(strat[:, 1] != strat[:, 0])
+
+
+@pytest.mark.parametrize("ld_dtype", [np.int8, np.float32], ids=["int8-on-the-fly", "fp32"])
+def test_ld_scores_of_an_upper_only_store_stay_in_the_upper_form(gpu, ld_dtype):
+    """`ld_scores(low_memory=False)` of LD objects that hold only the upper-triangular store scores them in that form: the
+    upper-form kernels over the same arrays as with ``low_memory=True``, hence the same bits.  Two chromosomes with a
+    single-SNP block, a small one and one past 64 SNPs."""
+    from viprs_amd.data import ArrayDataLoader
+    from viprs_amd.stats import ldsc
+    sizes = {1: [1, 5, 33, 70], 2: [3, 66]}
+    gdl = ArrayDataLoader.synthetic(sizes, ld_dtype=ld_dtype, forms=("upper",), ld_sample_size=400)
+    got = ldsc.ld_scores(gdl, low_memory=False, dequantize_on_the_fly=True)
+    want = ldsc.ld_scores(gdl, low_memory=True, dequantize_on_the_fly=True)
+    assert sorted(got) == sorted(want) == [1, 2]
+    for c in want:
+        assert got[c].shape == (sum(sizes[c]),) and np.all(np.isfinite(got[c])) and np.array_equal(got[c], want[c])
+        assert got[c][0] == 1.0 if c == 1 else got[c][0] > 1.0      # (the single-SNP block: the diagonal alone)

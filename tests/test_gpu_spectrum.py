@@ -307,3 +307,22 @@ def test_bits_are_the_replayed_model(gpu, case, T):
         assert np.all(want.status == 0) and 16 < want.iterations.max() < REPLAY_MAXITER
     finally:
         plan.close()
+
+
+@pytest.mark.parametrize("ld_dtype", [np.int8, np.float32], ids=["int8-on-the-fly", "fp32"])
+def test_ld_spectrum_mirrors_an_upper_only_store_on_the_device(gpu, ld_dtype):
+    """`ld_spectrum(low_memory=False)` of LD objects that hold only the upper-triangular store: mirrored on the device
+    (`LDPlan.from_upper`, documented as bit-identical to the symmetric plan), so every figure `==` the one of objects that
+    hand out the symmetric form themselves.  Two chromosomes with a single-SNP block, a small one and one past 64 SNPs."""
+    from viprs_amd.data import ArrayDataLoader
+    from viprs_amd.stats.spectrum import ld_spectrum
+    sizes = {1: [1, 5, 33, 70], 2: [3, 66]}
+    kw = dict(low_memory=False, dequantize_on_the_fly=True)
+    got = ld_spectrum(ArrayDataLoader.synthetic(sizes, ld_dtype=ld_dtype, forms=("upper",)), **kw)
+    want = ld_spectrum(ArrayDataLoader.synthetic(sizes, ld_dtype=ld_dtype), **kw)
+    assert sorted(got) == sorted(want) == [1, 2]
+    for c in want:
+        assert got[c]["min"] == want[c]["min"] and got[c]["max"] == want[c]["max"]
+        assert got[c]["per_block"].status.shape == (len(sizes[c]),) and got[c]["per_block"].converged
+        for field in FIELDS:
+            assert np.array_equal(getattr(got[c]["per_block"], field), getattr(want[c]["per_block"], field)), (c, field)

@@ -124,6 +124,18 @@ def test_simple_ldsc_against_the_formula():
     assert ldsc.ld_scores(bare, corrected=False, score_fn=ldsc.ld_scores_host)[None].shape == (33,)
 
 
+def test_ldsc_estimate_over_is_the_estimate_of_the_concatenations():
+    gdl = _gdl()
+    ss = gdl.sumstats_table
+    scores = ldsc.ld_scores(gdl, score_fn=ldsc.ld_scores_host)
+    for chroms in (sorted(ss), sorted(ss)[::-1], sorted(ss)[:1]):
+        want = ldsc.ldsc_estimate(np.concatenate([ldsc.chisq_statistic(ss[c]) for c in chroms]),
+                                  np.concatenate([scores[c] for c in chroms]),
+                                  np.concatenate([ss[c].n_per_snp for c in chroms]))
+        assert ldsc.ldsc_estimate_over(ss, scores, chroms) == want
+    assert ldsc.ldsc_estimate_over(ss, scores, sorted(ss)) == ldsc.simple_ldsc(gdl, ld_scores=scores)
+
+
 def test_zarr_store_answers_ld_scores(tmp_path):
     from viprs_amd.io.zarr_ld import ZarrLDMatrix, write_ld_store
     up = syn.make_ld([20, 13], low_memory=True, ld_dtype=np.int8, kind="longrange")

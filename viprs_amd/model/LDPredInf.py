@@ -20,7 +20,7 @@ import warnings
 import numpy as np
 
 from ..data import merge_ld_arrays
-from ._ld_loading import dequantize_scale, ld_load_dtype, load_ld_arrays
+from ._ld_loading import LoadedLD, ld_form, load_ld_in_order, open_plan
 
 
 class LDPredInf:
@@ -31,8 +31,11 @@ class LDPredInf:
         :param h2: heritability of the trait (a number in (0, 1]); None: the LD-score regression estimate
             (`viprs_amd.stats.ldsc.simple_ldsc` with corrected LD scores; needs the LD objects' ``sample_size``).
         :param float_precision: precision of the solve, 'float32' or 'float64'.
-        :param low_memory: load the upper-triangular form of the LD matrices.
-        :param dequantize_on_the_fly: keep integer LD in its stored dtype on the device.
+        :param low_memory: load the upper-triangular form of the LD matrices.  The LD is never expanded on the device:
+            with ``low_memory=False`` a matrix that holds only the upper-triangular store raises its ValueError.
+        :param dequantize_on_the_fly: keep integer LD in its stored dtype on the device.  Threaded through the chromosomes
+            in sorted order, as in `VIPRS`: the first float-stored chromosome turns it off for all later ones, and
+            ``dequantize_scale`` comes from the FIRST chromosome's matrix.
         :param device: HIP device index (default 0).
         :param solve_fn: test hook -- a callable ``(lb, ip, data, low_memory, b, shift, dq_scale, rtol, maxiter, x0) ->
             (x, info)`` that replaces the device solve.
@@ -54,8 +57,6 @@ class LDPredInf:
 
         ld_mats = gdl.get_ld_matrices()
         chroms = self.chromosomes
-        ld_data, ld_indptr, ld_left_bound = {}, {}, {}
-        self.std_beta = {}
         corr = None
         if h2 is None:
             from ..stats.ldsc import ld_correction
@@ -64,23 +65,21 @@ class LDPredInf:
             except ValueError as e:
                 raise ValueError("LDPredInf(h2=None) estimates h2 by LD-score regression (the reference's default, "
                                  f"magenpy.stats.h2.ldsc.simple_ldsc) -- {e}  Or pass h2.") from e
-        for c in chroms:
-            dtype, dequantize_on_the_fly = ld_load_dtype(ld_mats[c], dequantize_on_the_fly, float_precision)
-            lop, _ = load_ld_arrays(ld_mats[c], self.low_memory, dtype, expand_ld_on_device=False)
-            ld_data[c], ld_indptr[c], ld_left_bound[c] = lop.ld_data, lop.ld_indptr, lop.leftmost_idx
-            self.std_beta[c] = np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T)
-        self.dequantize_on_the_fly = dequantize_on_the_fly
-        self.dequantize_scale = dequantize_scale(ld_mats[chroms[0]], dequantize_on_the_fly)
+        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
+            ld_mats, chroms, self.low_memory, dequantize_on_the_fly, float_precision, expand_ld_on_device=False)
+        self.std_beta = {c: np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T) for c in chroms}
         # one plan over the concatenated chromosomes (LD blocks never span chromosomes)
-        lb, ip, data, self._seg = merge_ld_arrays(chroms, self.shapes, ld_left_bound, ld_indptr, ld_data)
+        lb, ip, data, self._seg = merge_ld_arrays(
+            chroms, self.shapes, {c: ld.left_bound for c, ld in loaded.items()}, {c: ld.indptr for c, ld in loaded.items()},
+            {c: ld.data for c, ld in loaded.items()})
+        del loaded
         self._plan = None
         if solve_fn is None:
             from .. import _lib
-            from ..plan import LDPlan
             if _lib.device_count() < 1:
                 raise RuntimeError("LDPredInf needs a HIP device: the solve has no CPU fallback")
             self.device = int(device) if device is not None else 0
-            self._plan = LDPlan(lb, ip, data, self.low_memory, device=self.device)
+            self._plan = open_plan(LoadedLD(lb, ip, data, ld_form(self.low_memory)), self.device)
         else:
             self._ld = (lb, ip, data)
         if h2 is None:
@@ -92,16 +91,13 @@ class LDPredInf:
     def _estimate_h2(self, lb, ip, data, corr, score_fn):
         """`simple_ldsc` over the model's own LD: corrected unit-weight scores of its plan (the host path: `score_fn` or
         `ld_scores_host`), then the estimate over all chromosomes."""
-        from ..stats.ldsc import chisq_statistic, ld_scores_host, ldsc_estimate
+        from ..stats.ldsc import ld_scores_host, ldsc_estimate_over
         if self._plan is not None and score_fn is None:
             scores = self._plan.ld_scores(None, corr, dq_scale=self.dequantize_scale, float_precision=self.float_precision)
         else:
             scores = (score_fn or ld_scores_host)(lb, ip, data, self.low_memory, None, corr, self.dequantize_scale)
         self.ld_score = {c: np.asarray(scores[a:e], dtype=np.float64) for c, (a, e) in self._seg.items()}
-        ss = self.gdl.sumstats_table
-        chroms = self.chromosomes
-        h2 = ldsc_estimate(np.concatenate([chisq_statistic(ss[c]) for c in chroms]), scores,
-                           np.concatenate([np.asarray(ss[c].n_per_snp, dtype=np.float64).ravel() for c in chroms]))
+        h2 = ldsc_estimate_over(self.gdl.sumstats_table, self.ld_score, self.chromosomes)
         if not 0.0 < h2 <= 1.0:
             raise ValueError(f"LDPredInf(h2=None): the LD-score regression estimate h2 = {h2!r} is not in (0, 1]; pass h2")
         return h2

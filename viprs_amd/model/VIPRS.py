@@ -25,7 +25,7 @@ import numpy as np
 
 from ..parallel import BlockShard, LocalComm, broadcast_from_root, shard_blocks
 from ..utils.optim import ConditionStreak, OptimizeResult
-from ._ld_loading import dequantize_scale, ld_load_dtype, load_ld_arrays
+from ._ld_loading import LoadedLD, empty_ld, ld_form, load_ld_in_order, open_plan
 
 logger = logging.getLogger(__name__)
 
@@ -44,11 +44,15 @@ def _is_numeric(x):
     return isinstance(x, (int, float, np.number, np.ndarray))
 
 
+def _is_compute(lambda_min):
+    """lambda_min='compute': the extremal eigenvalues of the LD the model holds, by Lanczos on its device."""
+    return isinstance(lambda_min, str) and lambda_min == "compute"
+
+
 def _pseudo_r2_external(validation_ld, std_beta, beta, device=0):
     """`viprs_amd.eval.pseudo_r2` of `beta` against an external panel: plans are made from ``(left_bound, indptr, data,
     low_memory)`` tuples and closed again, plans that are handed in stay open."""
     from ..eval.pseudo_metrics import pseudo_r2
-    from ..plan import LDPlan
     plans, own = {}, []
     try:
         for c in beta:
@@ -57,8 +61,7 @@ def _pseudo_r2_external(validation_ld, std_beta, beta, device=0):
             ld = validation_ld[c]
             if isinstance(ld, (tuple, list)):
                 lb, ip, data, low_memory = ld
-                ld = LDPlan(np.ascontiguousarray(lb, dtype=np.int32), np.ascontiguousarray(ip), np.ascontiguousarray(data),
-                            bool(low_memory), device=device)
+                ld = open_plan(LoadedLD.from_arrays(lb, ip, data, ld_form(low_memory)), device)
                 own.append(ld)
             plans[c] = ld
         return pseudo_r2(plans, std_beta, beta)
@@ -95,6 +98,10 @@ class VIPRS:
             memory and half the bytes cross PCIe.  ``None`` (default): only when the LD matrix cannot
             hand out the symmetric form itself.  The host attributes ``ld_data / ld_indptr /
             ld_left_bound`` then hold the upper-triangular arrays.
+
+        The stages, in order: `_check_arguments`, `_load_ld` (every chromosome -> `_ld_loading.LoadedLD`),
+        `_resolve_lambda_min`, `_deal_blocks` (several ranks), `_keep_local`, then `_build_device` (plans and states
+        through `_ld_loading.open_plan`) or, with ``e_step_fn``, the host model of the expansion.
         """
         if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
             raise AssertionError("The data loader must contain summary statistics and LD matrices.")
@@ -109,25 +116,8 @@ class VIPRS:
         self.order = order
         self.low_memory = low_memory
         self.math_mode = math_mode
-        if math_mode == "fast" and (self._T == np.float64 or getattr(self, "K", 1) > 8):
-            # (LDPlan.effective_math_mode() reports what a sweep really ran in)
-            import warnings
-            warnings.warn("math_mode='fast' has no kernels for " + ("float_precision='float64'" if self._T == np.float64 else
-                          f"mixtures of {self.K} components (> 8)") + ": this model runs in EXACT arithmetic", stacklevel=2)
         self._e_step_fn = e_step_fn
-        # lambda_min='compute': the extremal eigenvalues of the LD this model holds, by Lanczos on its device
-        compute_lambda = isinstance(lambda_min, str) and lambda_min == "compute"
-        if compute_lambda and e_step_fn is not None:
-            raise RuntimeError("lambda_min='compute' needs a HIP device: the Lanczos recurrence has no CPU fallback")
-        if compute_lambda and self.comm.world_size > 1:
-            raise NotImplementedError("lambda_min='compute' runs on one rank only (world_size > 1: annotate the LD "
-                                      "matrices with viprs_amd.stats.spectrum.annotate_spectrum and use 'infer')")
-
-        if not (h2_init is None or _is_numeric(h2_init) or (isinstance(h2_init, str) and h2_init == "ldsc")):
-            raise ValueError(f"h2_init: None, 'ldsc' or a number, got {h2_init!r}")
-        if isinstance(h2_init, str) and self.comm.world_size > 1:
-            raise NotImplementedError("h2_init='ldsc' runs on one rank only (world_size > 1: compute the estimate with "
-                                      "viprs_amd.stats.ldsc.simple_ldsc and pass it as a number)")
+        self._check_arguments(lambda_min, h2_init)
         self.h2_init = h2_init
         self._score_fn = score_fn
         self.h2_ldsc = None
@@ -137,149 +127,29 @@ class VIPRS:
         # independent unit of the E-step -- is assigned to one rank (chain-aware LPT over the blocks of
         # ALL chromosomes, `parallel.shard_blocks`), so a single-chromosome fit shards as well; each rank
         # keeps only the rows / per-SNP entries of its blocks, re-indexed to a local SNP numbering.
+        # All host loads finish before the first plan exists.
         self._all_shapes = dict(gdl.shapes)
         self._n_chroms_total = len(self._all_shapes)
         self._sample_size = max(float(np.max(s.n_per_snp)) for s in gdl.sumstats_table.values())
         ld_mats = gdl.get_ld_matrices()
-        world = self.comm.world_size
-        all_chroms = sorted(self._all_shapes)
-
-        self.ld_data, self.ld_indptr, self.ld_left_bound = {}, {}, {}
-        self.lambda_min = 0.0
-        self._expanded = False
-        loaded = {}
-        for c in all_chroms:
-            ld_mat = ld_mats[c]
-            dtype, dequantize_on_the_fly = ld_load_dtype(ld_mat, dequantize_on_the_fly, float_precision)
-            expand = bool(expand_ld_on_device) and not low_memory
-            # a store that can hand out row ranges (viprs_amd.io.zarr_ld.ZarrLDMatrix): with several ranks only the
-            # index is read here, the LD entries of this rank's blocks after the blocks have been dealt out
-            lazy = world > 1 and hasattr(ld_mat, "load_rows") and (low_memory or expand_ld_on_device is not False)
-            if lazy:
-                expand = not low_memory
-                self._expanded = self._expanded or expand
-                loaded[c] = (None, np.asarray(ld_mat.indptr()), np.arange(1, self._all_shapes[c] + 1, dtype=np.int32),
-                             ld_mat, dtype)
-            else:
-                lop, expanded = load_ld_arrays(ld_mat, low_memory, dtype, expand, expand_ld_on_device)
-                self._expanded = self._expanded or expanded
-                loaded[c] = (lop.ld_data, lop.ld_indptr, lop.leftmost_idx, None, dtype)
-            if lambda_min is None:
-                self.lambda_min = 0.0
-            elif _is_numeric(lambda_min):
-                self.lambda_min = lambda_min
-            elif compute_lambda:
-                pass                             # (below, once the LD is on the device)
-            else:                                # 'infer': the reference keeps the LAST chromosome's value (:186-191)
-                try:
-                    self.lambda_min = ld_mat.get_lambda_min(min_max_ratio=1e-3)
-                except NotImplementedError as e:     # (a store whose ridge formula this build cannot verify: say where, and the remedy)
-                    raise type(e)(f"lambda_min='infer', chromosome {c}: {e}  Remedy: VIPRS(..., lambda_min=<number>), or "
-                                  "set `lambda_min_formula` on the LD matrix object.") from e
-
-        self._shard = {}
-        self._block_owner = {}                   # chromosome -> (block starts, owning rank of every block)
-        if world > 1:
-            from ..plan import plan_blocks
-            upper_form = bool(low_memory) or self._expanded
-            starts = {c: plan_blocks(np.ascontiguousarray(loaded[c][2], dtype=np.int32), loaded[c][1], upper_form)[0]
-                      for c in all_chroms}
-            sizes = np.concatenate([np.diff(starts[c]) for c in all_chroms])
-            es = np.dtype(loaded[all_chroms[0]][4]).itemsize
-            owner = shard_blocks(sizes, world, es)
-            k = 0
-            for c in all_chroms:
-                nb = len(starts[c]) - 1
-                mine = [b for b in range(nb) if owner[k + b] == self.comm.rank]
-                self._block_owner[c] = (starts[c], np.asarray(owner[k:k + nb]))
-                k += nb
-                self._shard[c] = BlockShard(starts[c], mine)
-        self.shapes = {}
-        self.n_per_snp, self.std_beta = {}, {}
-        for c in all_chroms:
-            data, ip, lb, lazy_mat, dtype = loaded.pop(c)
-            sh = self._shard.get(c)
-            if sh is None:
-                self.shapes[c] = int(self._all_shapes[c])
-                self.ld_data[c], self.ld_indptr[c], self.ld_left_bound[c] = data, ip, lb
-                self.n_per_snp[c] = gdl.sumstats_table[c].n_per_snp
-                self.std_beta[c] = gdl.sumstats_table[c].get_snp_pseudo_corr().astype(self._T)
-            elif sh.m > 0:
-                self.shapes[c] = sh.m
-                if lazy_mat is not None:
-                    self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c] = sh.read_ld(lazy_mat, dtype)
-                else:
-                    self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c] = sh.slice_ld(
-                        np.asarray(lb), np.asarray(ip), data)
-                self.n_per_snp[c] = sh.take(gdl.sumstats_table[c].n_per_snp)
-                self.std_beta[c] = sh.take(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T)
-            del data
-        self.dequantize_on_the_fly = dequantize_on_the_fly
-        self.dequantize_scale = dequantize_scale(ld_mats[all_chroms[0]], dequantize_on_the_fly)          # :203-207
-
+        loaded = self._load_ld(ld_mats, dequantize_on_the_fly, expand_ld_on_device)
+        self._resolve_lambda_min(lambda_min, ld_mats)
+        self._deal_blocks(loaded)
+        self._keep_local(loaded)
         self._plans, self._dstate = {}, {}
+        self._resident = self._merged = self._device_reduce = False
         if e_step_fn is None:
-            from ..plan import DeviceState, LDPlan
-            from .. import _lib
-            ndev = _lib.device_count()
-            if ndev < 1:
-                raise RuntimeError("VIPRS needs a HIP device: the E-step has no CPU fallback")
-            self.device = int(device) if device is not None else self.comm.rank % ndev
-            self._resident = bool(device_resident) and self._supports_resident()
-            # several ranks: ONE plan per rank whatever the number of local chromosomes (one collective per EM
-            # iteration, per-SNP weights 1 / m_c of the FULL chromosome for the update_pi mean)
-            self._merged = (self._resident and bool(merge_chromosomes) and self._supports_merged()
-                            and (len(self.chromosomes) > 1 or world > 1 or self._always_merge))
-            if self._merged:
-                # one plan over the concatenated chromosomes: windows and row offsets shifted into place
-                from ..data import merge_ld_arrays
-                chroms = self.chromosomes
-                if chroms:
-                    lb, ip, data, self._seg = merge_ld_arrays(chroms, self.shapes, self.ld_left_bound, self.ld_indptr,
-                                                              self.ld_data)
-                else:                            # a rank without any LD block still takes part in the reductions
-                    ref = ld_mats[all_chroms[0]]
-                    lb, ip, self._seg = np.zeros(0, np.int32), np.zeros(1, np.int64), {}
-                    data = np.zeros(0, ref.stored_dtype if self.dequantize_on_the_fly else self._T)
-                if self._expanded:
-                    self._plans["*"] = LDPlan.from_upper(ip, data, device=self.device, math_mode=math_mode)
-                else:
-                    self._plans["*"] = LDPlan(lb, ip, data, low_memory, device=self.device, math_mode=math_mode)
-                del data
-                ds = self._dstate["*"] = self._make_device_state(self._plans["*"])
-                cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
-                ds.upload("std_beta", cat([self.std_beta[c] for c in chroms], self._T))
-                ds.set_n_per_snp(cat([np.asarray(self.n_per_snp[c], dtype=np.float64).ravel() for c in chroms], np.float64))
-                ds.set_snp_weights(cat([np.full(self.shapes[c], 1.0 / self._all_shapes[c]) for c in chroms], np.float64))
-                if getattr(self.comm, "device_side", False):
-                    ds.set_comm(self.comm)       # sums_begin / sums_end return the all-rank sums (RCCL, C ABI)
-                    self._device_reduce = True
-            else:
-                for c in self.chromosomes:
-                    if self._expanded:
-                        self._plans[c] = LDPlan.from_upper(self.ld_indptr[c], self.ld_data[c], device=self.device,
-                                                           math_mode=math_mode)
-                    else:
-                        self._plans[c] = LDPlan(self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c], low_memory,
-                                                device=self.device, math_mode=math_mode)
-                    self._dstate[c] = self._make_device_state(self._plans[c])
-                    self._dstate[c].upload("std_beta", self.std_beta[c])
-                if self._resident:
-                    for c in self.chromosomes:
-                        self._dstate[c].set_n_per_snp(self.n_per_snp[c])
-            if compute_lambda:
+            self._build_device(device, device_resident, merge_chromosomes, ld_mats)
+            if _is_compute(lambda_min):
                 self._compute_lambda_min()
-        else:
-            self._resident = self._merged = False
-            if self._expanded:          # test hook: the host model of the device-side expansion
-                from ..data import mirror_upper_ld
-                for c in self.chromosomes:
-                    self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c] = mirror_upper_ld(
-                        self.ld_indptr[c], self.ld_data[c])
-                self._expanded = False
+        elif self._expanded:                     # test hook: the host model of the device-side expansion
+            from ..data import mirror_upper_ld
+            for c in self.chromosomes:
+                self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c] = mirror_upper_ld(
+                    self.ld_indptr[c], self.ld_data[c])
+            self._expanded = False
         self._host_stale = False
         self._last_prep = None
-        self._device_reduce = getattr(self, "_device_reduce", False)
 
         # ---- model state -------------------------------------------------------------------------
         self.var_gamma, self.var_mu, self.var_tau, self._log_var_tau = {}, {}, {}, {}
@@ -291,6 +161,137 @@ class VIPRS:
         self._sums = None
         self._sums_valid = False
         self._max_eta_diff = 0.0
+
+    # ---- the stages of the constructor, in the order it runs them -------------------------------------
+    def _check_arguments(self, lambda_min, h2_init):
+        if self.math_mode == "fast" and (self._T == np.float64 or getattr(self, "K", 1) > 8):
+            # (LDPlan.effective_math_mode() reports what a sweep really ran in)
+            import warnings
+            warnings.warn("math_mode='fast' has no kernels for " + ("float_precision='float64'" if self._T == np.float64 else
+                          f"mixtures of {self.K} components (> 8)") + ": this model runs in EXACT arithmetic", stacklevel=3)
+        if _is_compute(lambda_min) and self._e_step_fn is not None:
+            raise RuntimeError("lambda_min='compute' needs a HIP device: the Lanczos recurrence has no CPU fallback")
+        if _is_compute(lambda_min) and self.comm.world_size > 1:
+            raise NotImplementedError("lambda_min='compute' runs on one rank only (world_size > 1: annotate the LD "
+                                      "matrices with viprs_amd.stats.spectrum.annotate_spectrum and use 'infer')")
+        if not (h2_init is None or _is_numeric(h2_init) or (isinstance(h2_init, str) and h2_init == "ldsc")):
+            raise ValueError(f"h2_init: None, 'ldsc' or a number, got {h2_init!r}")
+        if isinstance(h2_init, str) and self.comm.world_size > 1:
+            raise NotImplementedError("h2_init='ldsc' runs on one rank only (world_size > 1: compute the estimate with "
+                                      "viprs_amd.stats.ldsc.simple_ldsc and pass it as a number)")
+
+    def _load_ld(self, ld_mats, dequantize_on_the_fly, expand_ld_on_device):
+        """``{chromosome: LoadedLD}`` of ALL chromosomes (`load_ld_in_order`: `dequantize_on_the_fly` threaded through the
+        sorted chromosomes, `dequantize_scale` from the first one's matrix; with several ranks a store that can hand out
+        row ranges is read only as far as its index).  `_expanded`: some chromosome's upper store is to be mirrored."""
+        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
+            ld_mats, sorted(self._all_shapes), self.low_memory, dequantize_on_the_fly, self.float_precision,
+            expand_ld_on_device=expand_ld_on_device, index_only=self.comm.world_size > 1)
+        self._expanded = any(ld.form == "upper_to_expand" for ld in loaded.values())
+        return loaded
+
+    def _resolve_lambda_min(self, lambda_min, ld_mats):
+        """None: 0; a number: itself; 'compute': 0 until the LD is on the device (`_compute_lambda_min`); 'infer': what the
+        LD matrices answer -- the reference keeps the LAST chromosome's value (:186-191)."""
+        self.lambda_min = 0.0
+        if _is_numeric(lambda_min):
+            self.lambda_min = lambda_min
+        elif lambda_min is not None and not _is_compute(lambda_min):
+            for c in sorted(self._all_shapes):
+                try:
+                    self.lambda_min = ld_mats[c].get_lambda_min(min_max_ratio=1e-3)
+                except NotImplementedError as e:     # (a store whose ridge formula this build cannot verify: say where, and the remedy)
+                    raise type(e)(f"lambda_min='infer', chromosome {c}: {e}  Remedy: VIPRS(..., lambda_min=<number>), or "
+                                  "set `lambda_min_formula` on the LD matrix object.") from e
+
+    def _deal_blocks(self, loaded):
+        """Several ranks: `_shard` (this rank's blocks of every chromosome) and `_block_owner` (chromosome -> (block
+        starts, owning rank of every block)), identical on every rank.  The block starts come from the index alone
+        (`plan_blocks`, in the upper form when `low_memory` or expanded), the element size of the cost model from the first
+        chromosome's load dtype."""
+        self._shard, self._block_owner = {}, {}
+        if self.comm.world_size == 1:
+            return
+        from ..plan import plan_blocks
+        chroms = sorted(loaded)
+        upper_form = bool(self.low_memory) or self._expanded
+        starts = {c: plan_blocks(loaded[c].left_bound, loaded[c].indptr, upper_form)[0] for c in chroms}
+        sizes = np.concatenate([np.diff(starts[c]) for c in chroms])
+        owner = shard_blocks(sizes, self.comm.world_size, np.dtype(loaded[chroms[0]].dtype).itemsize)
+        k = 0
+        for c in chroms:
+            nb = len(starts[c]) - 1
+            mine = [b for b in range(nb) if owner[k + b] == self.comm.rank]
+            self._block_owner[c] = (starts[c], np.asarray(owner[k:k + nb]))
+            k += nb
+            self._shard[c] = BlockShard(starts[c], mine)
+
+    def _keep_local(self, loaded):
+        """The host attributes of the chromosomes this rank holds: everything with one rank, else the rows of its blocks
+        -- sliced from the loaded arrays, or read from a store of which only the index was loaded.  Empties `loaded`."""
+        ss = self.gdl.sumstats_table
+        self.shapes, self.n_per_snp, self.std_beta = {}, {}, {}
+        self.ld_data, self.ld_indptr, self.ld_left_bound = {}, {}, {}
+        for c in sorted(loaded):
+            ld = loaded.pop(c)
+            sh = self._shard.get(c)
+            if sh is None:
+                self.shapes[c] = int(self._all_shapes[c])
+                self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c] = ld.left_bound, ld.indptr, ld.data
+                self.n_per_snp[c] = ss[c].n_per_snp
+                self.std_beta[c] = ss[c].get_snp_pseudo_corr().astype(self._T)
+            elif sh.m > 0:
+                self.shapes[c] = sh.m
+                self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c] = (
+                    sh.read_ld(ld.ld_mat, ld.dtype) if ld.data is None else sh.slice_ld(ld.left_bound, ld.indptr, ld.data))
+                self.n_per_snp[c] = sh.take(ss[c].n_per_snp)
+                self.std_beta[c] = sh.take(ss[c].get_snp_pseudo_corr()).astype(self._T)
+
+    def _build_device(self, device, device_resident, merge_chromosomes, ld_mats):
+        """Plans and states, in sorted chromosome order.  Per chromosome: `set_n_per_snp` runs after all plans exist.
+        Merged: ``upload("std_beta")``, `set_n_per_snp`, `set_snp_weights`, `set_comm`.  (The state placement probe times
+        allocations: their order is part of what the benchmark measures.)"""
+        from .. import _lib
+        ndev = _lib.device_count()
+        if ndev < 1:
+            raise RuntimeError("VIPRS needs a HIP device: the E-step has no CPU fallback")
+        self.device = int(device) if device is not None else self.comm.rank % ndev
+        self._resident = bool(device_resident) and self._supports_resident()
+        form = ld_form(self.low_memory, self._expanded)
+        chroms = self.chromosomes
+        # several ranks: ONE plan per rank whatever the number of local chromosomes (one collective per EM
+        # iteration, per-SNP weights 1 / m_c of the FULL chromosome for the update_pi mean)
+        self._merged = (self._resident and bool(merge_chromosomes) and self._supports_merged()
+                        and (len(chroms) > 1 or self.comm.world_size > 1 or self._always_merge))
+        if self._merged:
+            # one plan over the concatenated chromosomes: windows and row offsets shifted into place
+            from ..data import merge_ld_arrays
+            if chroms:
+                merged = merge_ld_arrays(chroms, self.shapes, self.ld_left_bound, self.ld_indptr, self.ld_data)
+                ld, self._seg = LoadedLD(*merged[:3], form), merged[3]
+                del merged
+            else:                                # (its `data`: the stored dtype when dequantising, else the model's)
+                first = ld_mats[min(self._all_shapes)]
+                ld, self._seg = empty_ld(first.stored_dtype if self.dequantize_on_the_fly else self._T, form), {}
+            self._plans["*"] = open_plan(ld, self.device, self.math_mode)
+            del ld
+            ds = self._dstate["*"] = self._make_device_state(self._plans["*"])
+            cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
+            ds.upload("std_beta", cat([self.std_beta[c] for c in chroms], self._T))
+            ds.set_n_per_snp(cat([np.asarray(self.n_per_snp[c], dtype=np.float64).ravel() for c in chroms], np.float64))
+            ds.set_snp_weights(cat([np.full(self.shapes[c], 1.0 / self._all_shapes[c]) for c in chroms], np.float64))
+            if getattr(self.comm, "device_side", False):
+                ds.set_comm(self.comm)           # sums_begin / sums_end return the all-rank sums (RCCL, C ABI)
+                self._device_reduce = True
+            return
+        for c in chroms:
+            self._plans[c] = open_plan(LoadedLD(self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c], form),
+                                       self.device, self.math_mode)
+            self._dstate[c] = self._make_device_state(self._plans[c])
+            self._dstate[c].upload("std_beta", self.std_beta[c])
+        if self._resident:
+            for c in chroms:
+                self._dstate[c].set_n_per_snp(self.n_per_snp[c])
 
     def _compute_lambda_min(self):
         """lambda_min='compute': |min(smallest eigenvalue, 0)| of every chromosome's LD, from the extremal eigenvalues of
@@ -317,7 +318,7 @@ class VIPRS:
         applies when every LD object knows its ``sample_size``.  Computed once; ``ld_score`` keeps the scores."""
         if self.h2_ldsc is not None:
             return self.h2_ldsc
-        from ..stats.ldsc import chisq_statistic, ld_correction, ld_scores_host, ldsc_estimate
+        from ..stats.ldsc import ld_correction, ld_scores_host, ldsc_estimate_over
         ld_mats, ss = self.gdl.get_ld_matrices(), self.gdl.sumstats_table
         chroms = sorted(self.shapes)
         corrected = all(getattr(ld_mats[c], "sample_size", None) is not None for c in chroms)
@@ -335,10 +336,8 @@ class VIPRS:
             scores = {c: fn(self.ld_left_bound[c], self.ld_indptr[c], self.ld_data[c], upper, None, corr[c],
                             self.dequantize_scale) for c in chroms}
         self.ld_score = {c: np.asarray(scores[c], dtype=np.float64) for c in chroms}
-        chisq = {c: chisq_statistic(ss[c]) for c in chroms}
-        n = {c: np.asarray(ss[c].n_per_snp, dtype=np.float64).ravel() for c in chroms}
-        est = {c: ldsc_estimate(chisq[c], self.ld_score[c], n[c]) for c in chroms}
-        est["*"] = ldsc_estimate(*(np.concatenate([d[c] for c in chroms]) for d in (chisq, self.ld_score, n)))
+        est = {c: ldsc_estimate_over(ss, self.ld_score, [c]) for c in chroms}
+        est["*"] = ldsc_estimate_over(ss, self.ld_score, chroms)
         self.h2_ldsc = est
         return est
 

@@ -63,29 +63,26 @@ def ld_scores(ld_mat_or_gdl, annotation=None, corrected=True, low_memory=True, d
               float_precision="float32", score_fn=None):
     """LD scores of one LD matrix object, of a ``{chromosome: LD matrix}`` dict or of every chromosome of a data loader:
     ``{chromosome: array}``, ``(m_c,)`` or -- with `annotation`, an ``(m_c, G)`` array or a ``{chromosome: array}`` dict --
-    ``(m_c, G)``.  The LD is loaded as the models load it.  `corrected`: the adjusted r^2 with ``c = 1 / (n_LD - 2)`` from
-    the LD object's ``sample_size`` (ValueError when it has none).  On HIP device `device` (`LDPlan.ld_scores`); without a
-    device, or with `score_fn` (a callable with `ld_scores_host`'s signature), on the host in float64."""
+    ``(m_c, G)``.  The LD is loaded as the models load it (`load_chromosome_ld`), with two decisions of this function's own:
+    `dequantize_on_the_fly` is decided per matrix, and a matrix that holds only the upper-triangular store is scored in
+    that form with ``low_memory=False`` too, not mirrored (the scores of both forms are those of the same matrix).
+    `corrected`: the adjusted r^2 with ``c = 1 / (n_LD - 2)`` from the LD object's ``sample_size`` (ValueError when it has
+    none).  On HIP device `device` (`LDPlan.ld_scores`); without a device, or with `score_fn` (a callable with
+    `ld_scores_host`'s signature), on the host in float64."""
     from .. import _lib
-    from ..model._ld_loading import dequantize_scale, ld_load_dtype, load_ld_arrays
+    from ..model._ld_loading import dequantize_scale, load_chromosome_ld, open_plan
     on_host = score_fn is not None or _lib.device_count() < 1
     score_fn = score_fn or ld_scores_host
     out = {}
     for c, ld_mat in _ld_matrices(ld_mat_or_gdl).items():
-        dtype, deq = ld_load_dtype(ld_mat, dequantize_on_the_fly, float_precision)
-        lop, expanded = load_ld_arrays(ld_mat, low_memory, dtype)
-        upper = bool(low_memory) or expanded               # (the scores of both forms are those of the same matrix)
-        lb = np.ascontiguousarray(lop.leftmost_idx, dtype=np.int32)
-        ip, data = np.ascontiguousarray(lop.ld_indptr), np.ascontiguousarray(lop.ld_data)
-        m = lb.shape[0]
+        ld = load_chromosome_ld(ld_mat, low_memory, dequantize_on_the_fly, float_precision).as_stored()
         A = annotation[c] if isinstance(annotation, dict) else annotation
-        corr = ld_correction(ld_mat, m, where=f"chromosome {c}") if corrected else None
-        dq = dequantize_scale(ld_mat, deq)
+        corr = ld_correction(ld_mat, ld.left_bound.shape[0], where=f"chromosome {c}") if corrected else None
+        dq = dequantize_scale(ld_mat, ld.dequantize)
         if on_host:
-            out[c] = score_fn(lb, ip, data, upper, A, corr, dq)
+            out[c] = score_fn(ld.left_bound, ld.indptr, ld.data, ld.form == "upper", A, corr, dq)
             continue
-        from ..plan import LDPlan
-        plan = LDPlan(lb, ip, data, upper, device=device)
+        plan = open_plan(ld, device)
         try:
             A = None if A is None else np.asarray(A, dtype=float_precision)
             out[c] = plan.ld_scores(A, corr, dq_scale=dq, float_precision=float_precision)
@@ -125,6 +122,15 @@ def ldsc_estimate(chisq, ld_score, n_per_snp):
     return float((chisq.mean() - 1.0) * chisq.shape[0] / (ld_score.mean() * n.mean()))
 
 
+def ldsc_estimate_over(sumstats_table, scores, chroms):
+    """`ldsc_estimate` over the SNPs of the chromosomes `chroms`, concatenated in that order: chi2 and N from
+    ``sumstats_table[c]``, the LD scores from ``scores[c]``.  What `simple_ldsc`, `VIPRS(h2_init="ldsc")` and
+    `LDPredInf(h2=None)` report."""
+    return ldsc_estimate(np.concatenate([chisq_statistic(sumstats_table[c]) for c in chroms]),
+                         np.concatenate([np.asarray(scores[c], dtype=np.float64) for c in chroms]),
+                         np.concatenate([np.asarray(sumstats_table[c].n_per_snp, dtype=np.float64).ravel() for c in chroms]))
+
+
 def simple_ldsc(gdl, ld_scores=None, **kw):
     """The LD-score regression estimate of the SNP heritability without an intercept, over all chromosomes of the loader.
     `ld_scores`: ``{chromosome: (m_c,) array}``; else the scores attached to the LD objects where present, else they are
@@ -141,7 +147,4 @@ def simple_ldsc(gdl, ld_scores=None, **kw):
                 break
         if ld_scores is None:
             ld_scores = _compute_ld_scores(gdl, **kw)
-    ss = gdl.sumstats_table
-    return ldsc_estimate(np.concatenate([chisq_statistic(ss[c]) for c in chroms]),
-                         np.concatenate([np.asarray(ld_scores[c], dtype=np.float64) for c in chroms]),
-                         np.concatenate([np.asarray(ss[c].n_per_snp, dtype=np.float64).ravel() for c in chroms]))
+    return ldsc_estimate_over(gdl.sumstats_table, ld_scores, chroms)

@@ -13,8 +13,6 @@ and the extremes of a chromosome are the extremes over its blocks (the matrix is
 import json
 import os
 
-import numpy as np
-
 FORMULAS = ("one_plus_r", "one_minus_r")
 
 
@@ -81,24 +79,20 @@ def ld_spectrum(ld_mat_or_gdl, low_memory=True, dequantize_on_the_fly=False, dev
     """Extremal eigenvalues of one LD matrix object, of a ``{chromosome: LD matrix}`` dict or of every chromosome of a data
     loader, on HIP device `device`: ``{chromosome: {"min": ..., "max": ..., "per_block": SpectrumInfo}}``.  The LD is
     loaded as the models load it (`low_memory`: the upper-triangular form; `dequantize_on_the_fly`: integer LD stays in
-    its stored dtype on the device) -- the spectrum is that of the matrix the E-step multiplies with.  `kw`: ``rtol``,
-    ``maxiter`` of `LDPlan.extremal_eigenvalues`."""
+    its stored dtype on the device, decided per matrix) -- the spectrum is that of the matrix the E-step multiplies with.
+    With ``low_memory=False`` a matrix that holds only the upper-triangular store is mirrored on the device, as `VIPRS`
+    does by default.  `kw`: ``rtol``, ``maxiter`` of `LDPlan.extremal_eigenvalues`."""
     from .. import _lib
-    from ..model._ld_loading import dequantize_scale, ld_load_dtype, load_ld_arrays
-    from ..plan import LDPlan
+    from ..model._ld_loading import dequantize_scale, load_chromosome_ld, open_plan
     if _lib.device_count() < 1:
         raise RuntimeError("ld_spectrum needs a HIP device: the Lanczos recurrence has no CPU fallback")
     out = {}
     for c, ld_mat in _ld_matrices(ld_mat_or_gdl).items():
-        dtype, deq = ld_load_dtype(ld_mat, dequantize_on_the_fly, float_precision)
-        lop, expanded = load_ld_arrays(ld_mat, low_memory, dtype)
-        ip, data = np.ascontiguousarray(lop.ld_indptr), np.ascontiguousarray(lop.ld_data)
-        if expanded:
-            plan = LDPlan.from_upper(ip, data, device=device)
-        else:
-            plan = LDPlan(np.ascontiguousarray(lop.leftmost_idx, dtype=np.int32), ip, data, bool(low_memory), device=device)
+        ld = load_chromosome_ld(ld_mat, low_memory, dequantize_on_the_fly, float_precision)
+        plan = open_plan(ld, device)
         try:
-            out[c] = plan_spectrum(plan, dq_scale=dequantize_scale(ld_mat, deq), float_precision=float_precision, **kw)[None]
+            out[c] = plan_spectrum(plan, dq_scale=dequantize_scale(ld_mat, ld.dequantize), float_precision=float_precision,
+                                   **kw)[None]
         finally:
             plan.close()
     return out
