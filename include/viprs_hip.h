@@ -503,6 +503,41 @@ int viprs_plan_ld_scores(viprs_plan* plan, int float_dtype, int n_cols, const vo
                          void* scores_host, double dq_scale);
 int viprs_plan_last_ld_score_ms(viprs_plan* plan, double* ms);
 
+/* ---- greedy LD clumping: index_of[k, g] = the index SNP that claimed SNP k under threshold g ----------------------------
+ * The primitive of clumping + thresholding (C+T / P+T): walk the SNPs from the most significant down, make each unclaimed
+ * SNP an index SNP, and assign every SNP in LD with it above a threshold to its clump.  With the SNPs in natural order the
+ * same operation is LD pruning.  The definition is this library's own, stated in full.
+ *   order_host     n_order DISTINCT SNP indices in processing order, most significant first; n_order may be 0
+ *   member_host    (m,) bytes, non-zero = the SNP may belong to a clump; NULL = every SNP may.  Every SNP of `order` must be
+ *                  a member
+ *   r2_host        n_cols thresholds, 1 <= n_cols <= 32, each finite and >= 0
+ *   index_of_host  (m, n_cols) int32, column-major like every multi-column array of this header
+ * ENTRIES.  The entries of row j are exactly the entry set of viprs_plan_dot: the off-diagonal entries of the symmetric
+ * matrix the plan stands for; a stored zero is an entry, the gaps of a window and the diagonal are not; in the upper form
+ * the transposed entries (i, j) of the rows i < j that reach j belong to row j.
+ * PASS TEST.  An entry with stored element x passes column g iff (double)x * (double)x >= thr[g].  The host computes
+ * s2 = dq_scale * dq_scale and thr[g] = r2[g] / s2, two double operations.  The product is exact for int8, int16, int32
+ * and fp32 LD; for int64 and f64 LD it is rounded once, deterministically.
+ * PER COLUMN g, independently of the other columns:
+ *   1. avail = member, index_of[:, g] = -1
+ *   2. take j = order[0], order[1], ... in turn
+ *   3. if !avail[j], skip j
+ *   4. otherwise index_of[j, g] = j and avail[j] = 0
+ *   5. for every entry (j, k) with avail[k] that passes column g: index_of[k, g] = j and avail[k] = 0
+ * A column's result depends only on the plan's entries, `order`, `member` and that column's threshold: not on the other
+ * columns, not on which storage of the upper form the dense blocks are in, not on the active blocks
+ * (viprs_plan_set_active_blocks does NOT filter the call), not on timing.  The results are integers: two calls give
+ * identical values.  One workgroup per LD block (LD blocks share no entry), no atomics of any kind, no waiting on another
+ * workgroup.  On the plan's stream, synchronous; an upper-form plan that has not been swept yet is mirrored once, as for the
+ * product.  An empty plan returns VIPRS_OK.
+ * A null plan, output or r2, n_cols outside 1..32, a negative or non-finite threshold, dq_scale not finite or <= 0, an
+ * `order` entry out of range, repeated or not a member: VIPRS_EINVAL before any launch, `index_of_host` untouched.
+ *   viprs_plan_last_clump_ms  HIP-event time of the kernels of the last call on this plan; the sweeps' timing ring never
+ *                             sees the call */
+int viprs_plan_clump(viprs_plan* plan, int64_t n_order, const int32_t* order_host, const uint8_t* member_host,
+                     int n_cols, const double* r2_host, double dq_scale, int32_t* index_of_host);
+int viprs_plan_last_clump_ms(viprs_plan* plan, double* ms);
+
 /* ---- ridge solve: the LDPred-inf estimate, one MINRES per LD block -----------------------------------------------------
  * Solves (R + diag(shift)) x = b, independently for every LD block of the plan (blocks as viprs_plan_get_blocks lists
  * them, SNP order), by MINRES (Paige & Saunders 1975), x0 = 0 or the caller's. R = unit diagonal + dq_scale * stored

@@ -131,7 +131,9 @@ _PROTOS = {
     "viprs_plan_last_dot_ms": (_i, [_vp, ctypes.POINTER(_d)]),
     "viprs_plan_ld_scores": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d]),
     "viprs_plan_last_ld_score_ms": (_i, [_vp, ctypes.POINTER(_d)]),
-    "viprs_plan_solve_ridge": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _vp, _vp, _vp]),
+    "viprs_plan_clump": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _d, _vp]),
+    "viprs_plan_last_clump_ms": (_i, [_vp, ctypes.POINTER(_d)]),
+    "viprs_plan_solve_ridge":(_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _vp, _vp, _vp]),
     "viprs_plan_last_solve_ms": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_i)]),
     "viprs_plan_extremal_eigenvalues": (_i, [_vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "viprs_plan_last_spectrum_ms": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_i), ctypes.POINTER(_d)]),

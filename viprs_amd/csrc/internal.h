@@ -283,6 +283,14 @@ struct viprs_plan {
     viprs::DevBuf<char> d_score_a, d_score_y;
     viprs::DevBuf<double> d_score_corr;
     viprs::EventBracket time_score;
+    // LD clumping (abi_clump.hip, ld_clump.h): the product's tables; its own buffers and event pair
+    std::vector<int32_t> clump_block_of;           // the block of d_dot_blocks of every SNP (built by the first call)
+    viprs::DevBuf<int32_t> d_clump_order;          // the order, split stably by block of d_dot_blocks
+    viprs::DevBuf<int64_t> d_clump_off;            // blocks + 1 offsets of the pieces
+    viprs::DevBuf<double> d_clump_thr;             // 32 thresholds on the squared stored element
+    viprs::DevBuf<uint32_t> d_clump_mask;          // (m,) bit g set: the SNP is not available in column g
+    viprs::DevBuf<int32_t> d_clump_index;          // (m, n_cols) results
+    viprs::EventBracket time_clump;
     viprs::DevBuf<viprs::RidgeBlock> d_solver_blocks;   // start and size of every LD block, SNP order (ensure_solver_blocks)
     viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
     viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
@@ -396,5 +404,8 @@ template <typename U> int launch_ld_dot(viprs_plan* P, int float_dtype, int n_co
 // LD scores over every block of the plan (ld_score.h); device pointers, dA null: unit weights, dCorr null: no correction
 template <typename U> int launch_ld_score(viprs_plan* P, int float_dtype, int n_cols, const void* dA, const double* dCorr,
                                           void* dY, double dq_scale);
+// greedy clumping over every block of the plan (ld_clump.h): one workgroup per block of d_dot_blocks; the order pieces, the
+// thresholds, the masks and the results are the plan's d_clump_* buffers
+template <typename U> int launch_ld_clump(viprs_plan* P, int n_cols);
 
 }  // namespace viprs

@@ -1,0 +1,3 @@
+#define CLUMP_U int8_t
+#define CLUMP_DENSE 1
+#include "launch_ld_clump.inc"

@@ -346,6 +346,41 @@ class LDPlan:
         L.check(L.lib.viprs_plan_last_ld_score_ms(self.handle, ctypes.byref(ms)))
         return ms.value
 
+    # -- LD clumping --------------------------------------------------------------------------
+    def clump(self, order, r2, member=None, dq_scale=1.0):
+        """Greedy LD clumping over every block of the plan (`viprs_plan_clump`): `order` holds distinct SNP indices, most
+        significant first; each SNP of it that is still available becomes an index SNP and claims the available SNPs in LD
+        with it at ``(dq_scale * stored)^2 >= r2``.  Returns ``index_of``: int32 ``(m,)`` for a scalar `r2`, ``(m, G)``
+        (column-major) for a sequence of up to 32 thresholds, one independent clumping per column; -1 where no index SNP
+        claimed the SNP.  `member`: ``(m,)`` booleans, the SNPs that may belong to a clump (None: all); every SNP of `order`
+        must be one.  `set_active_blocks` does not filter the call."""
+        scalar = np.ndim(r2) == 0
+        thr = np.ascontiguousarray(np.atleast_1d(r2), dtype=np.float64)
+        if thr.ndim != 1:
+            raise ValueError(f"r2: expected a scalar or a 1-d sequence, got shape {thr.shape}")
+        o = np.asarray(order)
+        if o.ndim != 1 or (o.size and not np.issubdtype(o.dtype, np.integer)):
+            raise ValueError(f"order: expected a 1-d integer array, got {o.dtype} of shape {o.shape}")
+        if o.size and (int(o.min()) < 0 or int(o.max()) >= self.m):
+            raise ValueError(f"order: SNP indices must be in [0, {self.m})")
+        o = np.ascontiguousarray(o, dtype=np.int32)
+        mem = None
+        if member is not None:
+            mem = np.ascontiguousarray(np.asarray(member) != 0, dtype=np.uint8)
+            if mem.shape != (self.m,):
+                raise ValueError(f"member: expected shape ({self.m},), got {mem.shape}")
+        n_cols = int(thr.shape[0])
+        out = np.full((self.m, n_cols), -1, dtype=np.int32, order="F")
+        L.check(L.lib.viprs_plan_clump(self.handle, int(o.shape[0]), _ptr(o), _ptr(mem), n_cols, _ptr(thr), float(dq_scale),
+                                       _ptr(out)))
+        return out[:, 0] if scalar else out
+
+    def last_clump_ms(self):
+        """HIP-event time (ms) of the kernels of the last `clump` on this plan."""
+        ms = ctypes.c_double(0.0)
+        L.check(L.lib.viprs_plan_last_clump_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     # -- ridge solve -----------------------------------------------------------------------------
     def solve_ridge(self, b, shift, dq_scale=1.0, rtol=None, maxiter=None, x0=None, check_every=4):
         """``(R + diag(shift)) x = b`` by one MINRES per LD block, all blocks in lock step (`viprs_plan_solve_ridge`; what
