@@ -175,7 +175,10 @@ enum viprs_field {
     /* in/out state */
     VIPRS_FIELD_VAR_GAMMA = 5, VIPRS_FIELD_VAR_MU = 6, VIPRS_FIELD_ETA = 7, VIPRS_FIELD_Q = 8,
     VIPRS_FIELD_ETA_DIFF = 9,
-    VIPRS_FIELD_COUNT = 10
+    VIPRS_FIELD_COUNT = 10,
+    /* the two inputs of the elastic-net sweep (viprs_state_enet_sweep) live in fields of the E-step */
+    VIPRS_FIELD_ENET_MULT = VIPRS_FIELD_MU_MULT,                  /* c_j: lassosum's 1 - s */
+    VIPRS_FIELD_ENET_PENALTY = VIPRS_FIELD_SQRT_HALF_VAR_TAU      /* pen_j >= 0: lambda times an optional per-SNP factor */
 };
 
 /* `width` = 1 (spike-and-slab), K (mixture) or G (grid).                                      */
@@ -408,8 +411,10 @@ enum viprs_sweep_family {
     VIPRS_FAMILY_NONE = 0,           /* no launcher is called for the list */
     VIPRS_FAMILY_GENERIC = 1,        /* row-by-row kernels (called for an empty list too: they return at once) */
     VIPRS_FAMILY_TILE_F64 = 2,       /* float64 states: the panel-walking kernels (likewise) */
-    VIPRS_FAMILY_PANEL = 3,          /* the panel sweep; model 0 spike-and-slab, 1 grid column, 2 mixture K <= 8, 3 mixture K <= 31 */
-    VIPRS_FAMILY_BAND = 4,           /* band kernel of the windowed blocks; model 0 spike-and-slab, 1 grid column, 2 mixture */
+    VIPRS_FAMILY_PANEL = 3,          /* the panel sweep; model 0 spike-and-slab, 1 grid column, 2 mixture K <= 8, 3 mixture K <= 31
+                                        (4: the elastic net, viprs_enet_route only) */
+    VIPRS_FAMILY_BAND = 4,           /* band kernel of the windowed blocks; model 0 spike-and-slab, 1 grid column, 2 mixture
+                                        (3: the elastic net, viprs_enet_route only) */
     VIPRS_FAMILY_GRID_BATCHED = 5    /* batched grid kernel on the matrix cores: one launch per 32 active columns, a 1-model
                                         prologue launch in front of every launch after the first */
 };
@@ -426,6 +431,58 @@ enum viprs_route_field {
 };
 int viprs_sweep_route(int float_dtype, int model_kind, int width, int ld_dtype, int dense, int ragged, int band_ok,
                       int grid_mfma, int f64_row_by_row, int* route);
+
+/* ---- elastic net (lassosum): cyclic coordinate descent on the sweep of the E-step ------------------------------------------
+ * lassosum (Mak et al. 2017) estimates effects from marginal effects and an LD panel by minimising
+ *   beta' ((1 - s) R + s I) beta - 2 beta' std_beta + 2 sum_j pen_j |beta_j|
+ * by cyclic coordinate descent over each LD block with a running q = (R - I) beta: the serial Gauss-Seidel chain of
+ * viprs_state_e_step with a soft threshold where the E-step has a sigmoid.  The reference has no such model; the definition
+ * is this library's own, stated in full.
+ *   viprs_state_enet_sweep  one sweep over every LD block the plan's sweeps visit (viprs_plan_set_active_blocks filters it
+ *                           as it filters the E-step), on an fp32 state of kind VIPRS_MODEL_SPIKE_SLAB (width 1) or
+ *                           VIPRS_MODEL_GRID (width G: every column its own c, pen, eta, q); asynchronous on the plan's
+ *                           stream unless `sync` != 0
+ * THE UPDATE.  Per SNP j in index order, and per column of a grid state, from the current q_j, every operation separately
+ * rounded in float32, no fused multiply-add:
+ *   t = fl(c_j * q_j)
+ *   u = fl(std_beta_j - t)
+ *   a = fl(|u| - pen_j)
+ *   b = a > 0 ? copysign(a, u) : +0
+ *   d = fl(b - eta_old_j)
+ *   var_mu[j] = u;  var_gamma[j] = (b != 0) ? 1 : 0;  eta_diff[j] = d;  eta[j] = fl(eta_old_j + d)
+ * then the E-step's own update of q over the row's window in index order, q[k] = fma(R[j,k], dq_scale * d, q[k]) (symmetric
+ * form: followed by q[j] -= d, e_step.hpp:423-428), and after the block the second pass of the upper form, update_q_factor
+ * (e_step.hpp:331-337): q[j] += dq_scale * dot(row(j), eta_diff) with the dot a serial fma chain from 0 in index order.
+ * There is no skip branch: a zero d is added like any other and leaves the bits of q alone.  No random numbers, no
+ * transcendental function: a sweep is a function of the state and the LD alone, two calls give identical bits.
+ *   c_j    VIPRS_FIELD_ENET_MULT (= VIPRS_FIELD_MU_MULT): lassosum's 1 - s
+ *   pen_j  VIPRS_FIELD_ENET_PENALTY (= VIPRS_FIELD_SQRT_HALF_VAR_TAU): lambda times an optional per-SNP penalty factor, >= 0
+ *   VIPRS_FIELD_U_LOGS is not read.  With a constant c = 1 - s a fixed point of the sweep minimises the objective above.
+ * KERNELS.  The panel sweep serves the dense blocks and the band kernel the windowed ones, for fp32, int8 and int16 LD in both
+ * forms; the columns of a grid state run as (block, model) items of ONE panel launch, never on the batched matrix-core
+ * kernel; `active_model_idx` / `n_active` as in viprs_state_e_step (NULL: every column; ignored for width 1).  The kernel is
+ * the same in either math_mode: viprs_plan_last_math_modes reports exact.  Timing goes through the plan's timing record of
+ * the sweeps (viprs_plan_last_kernel_ms, viprs_plan_timing_history).
+ * REFUSALS, each before any launch: a float64 state VIPRS_EUNSUPPORTED; a mixture state VIPRS_EINVAL; a grid state under a
+ * (group, column) mask VIPRS_EUNSUPPORTED; windowed blocks the band kernel cannot take (VIPRS_BAND=0, or a window wider than
+ * its q ring) VIPRS_EUNSUPPORTED -- there is no row-by-row kernel for this update.
+ *   viprs_enet_route        the route of such a sweep (pure host code; usable without a GPU), the VIPRS_ROUTE_COUNT fields of
+ *                           viprs_sweep_route: dense blocks VIPRS_FAMILY_PANEL with model 4, windowed blocks
+ *                           VIPRS_FAMILY_BAND with model 3; prologue and events as the spike-and-slab row of viprs_sweep_route
+ *                           for width 1 (`grid` == 0) and as its grid row for a grid state.  viprs_sweep_route itself does
+ *                           not know the elastic net: its arguments and answers are unchanged
+ *   viprs_state_enet_sums   `out`: n rows of VIPRS_N_ENET_SUMS doubles, one per listed column (`cols` NULL: columns
+ *                           0 .. n - 1 with n = the state's width; width 1: n = 1):
+ *                             [0] max |eta_diff| (fmax: ignores NaN)   [1] sum std_beta eta   [2] sum q eta   [3] sum eta^2
+ *                             [4] sum pen |eta|   [5] the number of eta != 0
+ *                           every term formed in double from the float32 values (no fma), summed in THE ORDER defined above
+ *                           for the rows of a spike-and-slab or grid state (cap 1024 / 256 workgroups).  Synchronous.  With
+ *                           viprs_state_set_comm the rows are all-rank sums.  With a constant c = 1 - s the objective above
+ *                           is (1 - s) ([2] + [3]) + s [3] - 2 [1] + 2 [4]. */
+#define VIPRS_N_ENET_SUMS 6
+int viprs_state_enet_sweep(viprs_state* state, double dq_scale, const int32_t* active_model_idx, int n_active, int sync);
+int viprs_state_enet_sums(viprs_state* state, int n, const int32_t* cols, double* out);
+int viprs_enet_route(int grid, int ld_dtype, int dense, int ragged, int band_ok, int* route);
 
 /* ---- LD product: Y = R B over EVERY block of a plan -------------------------------------------------------------------
  * What the reference computes with `ld.dot(B)`: the pseudo-validation metrics against a validation LD panel

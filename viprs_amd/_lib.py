@@ -29,6 +29,9 @@ ROUTE_FIELDS = ("dense_family", "dense_model", "ragged_family", "ragged_model", 
 
 OK, EINVAL, ELAYOUT, EDEVICE, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 N_SUMS = 11
+N_ENET_SUMS = 6
+FIELD_ENET_MULT, FIELD_ENET_PENALTY = FIELD_MU_MULT, FIELD_SQRT_HALF_VAR_TAU
+PANEL_ELASTIC_NET, BAND_ELASTIC_NET = 4, 3          # model constants of the elastic-net route (viprs_enet_route)
 COMM_ID_BYTES = 128
 
 
@@ -126,6 +129,9 @@ _PROTOS = {
     "viprs_plan_timing_reset": (_i, [_vp]),
     "viprs_plan_timing_history": (_i, [_vp, _i, ctypes.POINTER(_d), _i, ctypes.POINTER(_i)]),
     "viprs_sweep_route": (_i, [_i] * 9 + [ctypes.POINTER(_i)]),
+    "viprs_state_enet_sweep": (_i, [_vp, _d, _vp, _i, _i]),
+    "viprs_state_enet_sums": (_i, [_vp, _i, _vp, _vp]),
+    "viprs_enet_route": (_i, [_i] * 5 + [ctypes.POINTER(_i)]),
     "viprs_plan_dot": (_i, [_vp, _i, _i, _vp, _vp, _d, _i]),
     "viprs_state_dot": (_i, [_vp, _i, _d, _i, _vp]),
     "viprs_plan_last_dot_ms": (_i, [_vp, ctypes.POINTER(_d)]),
@@ -196,4 +202,11 @@ def sweep_route(float_dtype, model_kind, width, ld_dtype, dense, ragged, band_ok
     out = (_i * len(ROUTE_FIELDS))()
     check(lib.viprs_sweep_route(float_dtype, model_kind, width, ld_dtype, int(dense), int(ragged), int(band_ok),
                                 int(grid_mfma), int(f64_row_by_row), out))
+    return dict(zip(ROUTE_FIELDS, out))
+
+
+def enet_route(grid, ld_dtype, dense, ragged, band_ok=True):
+    """The route of an elastic-net sweep (`viprs_enet_route`, include/viprs_hip.h) as a dict over ROUTE_FIELDS; needs no GPU."""
+    out = (_i * len(ROUTE_FIELDS))()
+    check(lib.viprs_enet_route(int(bool(grid)), ld_dtype, int(dense), int(ragged), int(band_ok), out))
     return dict(zip(ROUTE_FIELDS, out))

@@ -122,12 +122,13 @@ int launch_family(viprs_state* S, const EStepArgs<T>& A, int family, int model, 
                 return launch_tile_f64<decltype(u)>(P, A, model, dense); });
     } else {
         // (kPanelGridColumn: ONE launch over (block, model) work items, select_model offsets the columns in-kernel)
+        // (the elastic-net policy has its own translation units and launchers: launch_panel_enet.inc, launch_band_enet.inc)
         if (family == kFamPanel)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
-                return launch_panel<decltype(u)>(P, A, model); });
+                return model == kPanelElasticNet ? launch_panel_enet<decltype(u)>(P, A) : launch_panel<decltype(u)>(P, A, model); });
         if (family == kFamBand)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kBandLdTypeError, [&](auto u) {
-                return launch_band<decltype(u)>(P, A, model); });
+                return model == kBandElasticNet ? launch_band_enet<decltype(u)>(P, A) : launch_band<decltype(u)>(P, A, model); });
         if (family == kFamGridBatched)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
                 return launch_grid_chunks<decltype(u)>(S, A); });
@@ -169,18 +170,10 @@ bool use_grid_mfma(const viprs_plan* P, int width) {
     return (int64_t)P->dense_h.size() * 8 >= (int64_t)P->n_cu * 3;
 }
 
-// One sweep of any model: the route (sweep_route.h) says which kernel family serves which block list, whether the prologue
-// launch is needed and which events are recorded; this function executes it.
-int run_sweep(viprs_state* S, double dq, const int32_t* d_active, int n_active) {
-    static_assert(kGenSpikeSlab == VIPRS_MODEL_SPIKE_SLAB && kGenMixture == VIPRS_MODEL_MIXTURE && kGenGrid == VIPRS_MODEL_GRID, "");
+// Executes a route (sweep_route.h): the prologue launch where the route asks for one, the timing slot, the launchers.
+int run_route(viprs_state* S, const SweepRoute& r, double dq, const int32_t* d_active, int n_active) {
     viprs_plan* P = S->plan;
-    HIP_TRY(hipSetDevice(P->device));
-    const SweepConfig c{S->float_dtype, S->model_kind, S->width, P->ld_dtype, !P->dense_h.empty(), !P->ragged_h.empty(), band_ok(P),
-                        use_grid_mfma(P, S->width), getenv("VIPRS_F64_ROW_BY_ROW") != nullptr};
-    SweepRoute r;
-    std::string err;
-    int rc = sweep_route(c, r, err);
-    if (rc != VIPRS_OK) return fail(rc, err);
+    int rc = VIPRS_OK;
     // begin the sweep: the books of the kernels, then the timing slot
     if (r.prologue) rc = sweep_prologue(P, r.prologue_per_model ? n_active : 1);
     else HIP_TRY(clear_stale_skip_count(P));
@@ -194,6 +187,21 @@ int run_sweep(viprs_state* S, double dq, const int32_t* d_active, int n_active) 
                                      : launch_route<double>(S, r, dq, d_active, n_active);
     if (rc != VIPRS_OK) { P->timing.abandon(); return rc; }
     return P->timing.close();
+}
+
+// One sweep of any model: the route (sweep_route.h) says which kernel family serves which block list, whether the prologue
+// launch is needed and which events are recorded; run_route executes it.
+int run_sweep(viprs_state* S, double dq, const int32_t* d_active, int n_active) {
+    static_assert(kGenSpikeSlab == VIPRS_MODEL_SPIKE_SLAB && kGenMixture == VIPRS_MODEL_MIXTURE && kGenGrid == VIPRS_MODEL_GRID, "");
+    viprs_plan* P = S->plan;
+    HIP_TRY(hipSetDevice(P->device));
+    const SweepConfig c{S->float_dtype, S->model_kind, S->width, P->ld_dtype, !P->dense_h.empty(), !P->ragged_h.empty(), band_ok(P),
+                        use_grid_mfma(P, S->width), getenv("VIPRS_F64_ROW_BY_ROW") != nullptr};
+    SweepRoute r;
+    std::string err;
+    const int rc = sweep_route(c, r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    return run_route(S, r, dq, d_active, n_active);
 }
 
 // A grid state with SNP groups under a (group, column) mask (viprs_state_set_group_columns): the batched matrix-core kernel
@@ -237,6 +245,33 @@ int group_mask_prepare(viprs_state* S, const int32_t* active, int n_active) {
     return VIPRS_OK;
 }
 
+// The active list of a grid sweep: null = every model (`all` then holds the list); VIPRS_EINVAL for an index out of range.
+int active_list_check(const viprs_state* S, const int32_t*& active, int& n_active, std::vector<int32_t>& all) {
+    if (!active) {
+        all.resize((size_t)S->width);
+        for (int g = 0; g < S->width; ++g) all[(size_t)g] = g;
+        active = all.data();
+        n_active = S->width;
+    }
+    for (int i = 0; i < n_active; ++i)
+        if (active[i] < 0 || active[i] >= S->width) return fail(VIPRS_EINVAL, "active_model_idx out of range");
+    return VIPRS_OK;
+}
+
+int active_list_upload(viprs_state* S, const int32_t* active, int n_active) {
+    if (S->d_active.n < (size_t)n_active) HIP_TRY(S->d_active.alloc((size_t)std::max(n_active, S->width)));
+    HIP_TRY(hipMemcpyAsync(S->d_active.p, active, sizeof(int32_t) * (size_t)n_active, hipMemcpyHostToDevice, S->plan->stream));
+    HIP_TRY(hipStreamSynchronize(S->plan->stream));   // `active` may be a temporary
+    return VIPRS_OK;
+}
+
+// the fields of viprs_route_field, in the order of the enum
+void route_fields(const SweepRoute& r, int* route) {
+    const int out[VIPRS_ROUTE_COUNT] = {r.dense_family, r.dense_model, r.ragged_family, r.ragged_model, r.prologue,
+                                        r.prologue_per_model, r.start_event_by_launcher, r.whole_sweep_events, r.dense_bracketed};
+    std::copy(out, out + VIPRS_ROUTE_COUNT, route);
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,24 +283,16 @@ int viprs_state_e_step(viprs_state* S, double dq_scale, const int32_t* active, i
         case VIPRS_MODEL_SPIKE_SLAB: case VIPRS_MODEL_MIXTURE: rc = run_sweep(S, dq_scale, nullptr, 0); break;
         case VIPRS_MODEL_GRID: {
             std::vector<int32_t> all;
-            if (!active) {                                    // default: every model is active
-                all.resize((size_t)S->width);
-                for (int g = 0; g < S->width; ++g) all[(size_t)g] = g;
-                active = all.data();
-                n_active = S->width;
-            }
-            for (int i = 0; i < n_active; ++i)
-                if (active[i] < 0 || active[i] >= S->width) return fail(VIPRS_EINVAL, "active_model_idx out of range");
+            rc = active_list_check(S, active, n_active, all);
+            if (rc != VIPRS_OK) return rc;
             if (n_active == 0) return VIPRS_OK;
             HIP_TRY(hipSetDevice(S->plan->device));
             if (!S->group_cols_h.empty()) {
                 rc = group_mask_prepare(S, active, n_active);
                 if (rc != VIPRS_OK) return rc;
             }
-            if (S->d_active.n < (size_t)n_active) HIP_TRY(S->d_active.alloc((size_t)std::max(n_active, S->width)));
-            HIP_TRY(hipMemcpyAsync(S->d_active.p, active, sizeof(int32_t) * (size_t)n_active, hipMemcpyHostToDevice,
-                                   S->plan->stream));
-            HIP_TRY(hipStreamSynchronize(S->plan->stream));   // `active` may be a temporary
+            rc = active_list_upload(S, active, n_active);
+            if (rc != VIPRS_OK) return rc;
             rc = run_sweep(S, dq_scale, S->d_active.p, n_active);
             break;
         }
@@ -273,6 +300,51 @@ int viprs_state_e_step(viprs_state* S, double dq_scale, const int32_t* active, i
     }
     if (rc != VIPRS_OK) return rc;
     if (sync) HIP_TRY(hipStreamSynchronize(S->plan->stream));
+    return VIPRS_OK;
+}
+
+int viprs_state_enet_sweep(viprs_state* S, double dq_scale, const int32_t* active, int n_active, int sync) {
+    if (!S) return fail(VIPRS_EINVAL, "null state");
+    // every refusal comes before the first launch
+    if (S->model_kind == VIPRS_MODEL_MIXTURE) return fail(VIPRS_EINVAL, "elastic-net sweep: not defined for a mixture state");
+    if (S->model_kind != VIPRS_MODEL_SPIKE_SLAB && S->model_kind != VIPRS_MODEL_GRID) return fail(VIPRS_EINVAL, "bad model kind");
+    if (S->float_dtype != VIPRS_F32)
+        return fail(VIPRS_EUNSUPPORTED, "elastic-net sweep: float64 states are not supported (the kernels are float32)");
+    const bool grid = S->model_kind == VIPRS_MODEL_GRID;
+    if (grid && !S->group_cols_h.empty())
+        return fail(VIPRS_EUNSUPPORTED, "elastic-net sweep: a grid state under a (group, column) mask is not supported");
+    viprs_plan* P = S->plan;
+    std::vector<int32_t> all;
+    if (grid) {
+        const int rc = active_list_check(S, active, n_active, all);
+        if (rc != VIPRS_OK) return rc;
+    } else {
+        active = nullptr;
+        n_active = 0;
+    }
+    SweepRoute r;
+    std::string err;
+    int rc = enet_route(grid, P->ld_dtype, !P->dense_h.empty(), !P->ragged_h.empty(), band_ok(P), r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    if (grid && n_active == 0) return VIPRS_OK;
+    HIP_TRY(hipSetDevice(P->device));
+    if (grid) {
+        rc = active_list_upload(S, active, n_active);
+        if (rc != VIPRS_OK) return rc;
+    }
+    rc = run_route(S, r, dq_scale, grid ? S->d_active.p : nullptr, n_active);
+    if (rc != VIPRS_OK) return rc;
+    if (sync) HIP_TRY(hipStreamSynchronize(P->stream));
+    return VIPRS_OK;
+}
+
+int viprs_enet_route(int grid, int ld_dtype, int dense, int ragged, int band_ok, int* route) {
+    if (!route) return fail(VIPRS_EINVAL, "null argument");
+    SweepRoute r;
+    std::string err;
+    const int rc = enet_route(grid != 0, ld_dtype, dense != 0, ragged != 0, band_ok != 0, r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    route_fields(r, route);
     return VIPRS_OK;
 }
 
@@ -385,9 +457,7 @@ int viprs_sweep_route(int float_dtype, int model_kind, int width, int ld_dtype, 
     std::string err;
     const int rc = sweep_route(c, r, err);
     if (rc != VIPRS_OK) return fail(rc, err);
-    const int out[VIPRS_ROUTE_COUNT] = {r.dense_family, r.dense_model, r.ragged_family, r.ragged_model, r.prologue,
-                                        r.prologue_per_model, r.start_event_by_launcher, r.whole_sweep_events, r.dense_bracketed};
-    std::copy(out, out + VIPRS_ROUTE_COUNT, route);
+    route_fields(r, route);
     return VIPRS_OK;
 }
 

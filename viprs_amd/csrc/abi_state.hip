@@ -258,6 +258,46 @@ __global__ __launch_bounds__(kSumsBlock) void sums_mixture_kernel(int K, SumsRow
                          r.one_plus_lambda, partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kMixSums(K));
 }
 
+// The sums of the elastic-net sweep (viprs_state_enet_sums), fp32 states: the row scheme of sums_kernel -- workgroup `bx` of
+// `nb` over SNPs [i0, i1), the same serial order per thread, the same tree -- with the maximum LAST in the partials, where
+// sums_final_kernel and the all-rank reduction expect it (the entry point moves it to the front).
+constexpr int kNEnetSums = VIPRS_N_ENET_SUMS;
+__global__ __launch_bounds__(kSumsBlock) void enet_sums_kernel(SumsRow one, const SumsRow* __restrict__ rows,
+                                                               const float* __restrict__ eta, const float* __restrict__ q,
+                                                               const float* __restrict__ ed, const float* __restrict__ beta,
+                                                               const float* __restrict__ pen, double* __restrict__ partials) {
+    SumsRow r;
+    if (rows) r = rows[blockIdx.y];
+    else r = one;
+    if ((int)blockIdx.x >= r.nb) return;
+    __shared__ double red[kNEnetSums][kSumsBlock];
+    double acc[kNEnetSums];
+#pragma unroll
+    for (int k = 0; k < kNEnetSums; ++k) acc[k] = 0.0;
+    for (int64_t i = r.i0 + (int64_t)blockIdx.x * kSumsBlock + threadIdx.x; i < r.i1; i += (int64_t)r.nb * kSumsBlock) {
+        const double e = (double)eta[r.off + i];
+        acc[0] += (double)beta[i] * e;
+        acc[1] += (double)q[r.off + i] * e;
+        acc[2] += e * e;
+        acc[3] += (double)pen[r.off + i] * fabs(e);
+        acc[4] += e != 0.0 ? 1.0 : 0.0;
+        acc[5] = fmax(acc[5], fabs((double)ed[r.off + i]));
+    }
+#pragma unroll
+    for (int k = 0; k < kNEnetSums; ++k) red[k][threadIdx.x] = acc[k];
+    __syncthreads();
+    for (int s = kSumsBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+#pragma unroll
+            for (int k = 0; k < kNEnetSums - 1; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+            red[kNEnetSums - 1][threadIdx.x] = fmax(red[kNEnetSums - 1][threadIdx.x], red[kNEnetSums - 1][threadIdx.x + s]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < kNEnetSums)
+        partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kNEnetSums + threadIdx.x] = red[threadIdx.x][0];
+}
+
 // stage 2, every family: workgroup (k, y) is one wave adding sum k over the `nb` partials of row y (`stride` slots per row):
 // lane l adds the partials of workgroups l, l + 64, ... in order, then a fixed xor-shuffle tree combines the 64 lanes -- a
 // deterministic order whatever the timing; the last sum of a row is a maximum
@@ -514,10 +554,14 @@ static int sums_buffers(viprs_state* S, size_t partials, size_t total) {
     return VIPRS_OK;
 }
 
+// the first-stage kernel of a reduction (callers that pass a bool mean the first two)
+enum { kSumsSpikeSlabOrGrid = 0, kSumsMixture = 1, kSumsElasticNet = 2 };
+
 // Enqueues the reduction of `one` (kernel argument) or of the `n` rows in the sums staging (one H2D copy), n_sums sums per
-// row, then the all-rank reduction and the asynchronous copy into h_sums; sums_collect waits for it.  A rank whose plan
+// row, by the first-stage kernel `family`, then the all-rank reduction and the asynchronous copy into h_sums; sums_collect waits for it.  A rank whose plan
 // holds no SNP contributes zeros to the collective of viprs_state_set_comm.
-static int sums_enqueue(viprs_state* S, bool mixture, int n, int n_sums, const SumsRow* one) {
+static int sums_enqueue(viprs_state* S, int family, int n, int n_sums, const SumsRow* one) {
+    const bool mixture = family == kSumsMixture;
     viprs_plan* P = S->plan;
     HIP_TRY(hipSetDevice(P->device));
     const size_t total = (size_t)n * n_sums;
@@ -536,7 +580,12 @@ static int sums_enqueue(viprs_state* S, bool mixture, int n, int n_sums, const S
     *h, rows, (const T*)S->f[VIPRS_FIELD_VAR_GAMMA].p, (const T*)S->f[VIPRS_FIELD_VAR_MU].p, (const T*)S->f[VIPRS_FIELD_ETA].p, \
         (const T*)S->f[VIPRS_FIELD_Q].p, (const T*)S->f[VIPRS_FIELD_ETA_DIFF].p, (const T*)S->f[VIPRS_FIELD_STD_BETA].p,       \
         S->d_var_tau.p
-        if (mixture && S->float_dtype == VIPRS_F32)
+        if (family == kSumsElasticNet)
+            enet_sums_kernel<<<grid, kSumsBlock, 0, P->stream>>>(
+                *h, rows, (const float*)S->f[VIPRS_FIELD_ETA].p, (const float*)S->f[VIPRS_FIELD_Q].p,
+                (const float*)S->f[VIPRS_FIELD_ETA_DIFF].p, (const float*)S->f[VIPRS_FIELD_STD_BETA].p,
+                (const float*)S->f[VIPRS_FIELD_ENET_PENALTY].p, S->d_partials.p);
+        else if (mixture && S->float_dtype == VIPRS_F32)
             sums_mixture_kernel<float><<<grid, kSumsBlock, 0, P->stream>>>(S->width, VIPRS_SUMS_ARGS(float), S->d_log_var_tau0.p,
                                                                            S->d_partials.p);
         else if (mixture)
@@ -802,6 +851,40 @@ int viprs_state_sums_columns_begin(viprs_state* S, int n, const double* cols) {
     for (int i = 0; i < n; ++i)
         h[i] = sums_row(S, 0, P->m, (int64_t)cols[2 * i], cols[2 * i + 1], true, col_last_prep(S, (int)cols[2 * i]));
     return sums_enqueue(S, false, n, kNSums, nullptr);
+}
+
+int viprs_state_enet_sums(viprs_state* S, int n, const int32_t* cols, double* out) {
+    if (!S || !out) return fail(VIPRS_EINVAL, "null argument");
+    if (S->model_kind == VIPRS_MODEL_MIXTURE) return fail(VIPRS_EINVAL, "elastic-net sums: not defined for a mixture state");
+    if (S->float_dtype != VIPRS_F32) return fail(VIPRS_EUNSUPPORTED, "elastic-net sums: float64 states are not supported");
+    const bool grid = S->model_kind == VIPRS_MODEL_GRID;
+    if (n < 0 || n > S->width) return fail(VIPRS_EINVAL, "bad column count");
+    if (!cols && n != S->width) return fail(VIPRS_EINVAL, "cols == NULL lists every column: n must be the state's width");
+    for (int i = 0; cols && i < n; ++i)
+        if (cols[i] < 0 || cols[i] >= S->width) return fail(VIPRS_EINVAL, "model index out of range");
+    viprs_plan* P = S->plan;
+    for (int k = 0; k < n * kNEnetSums; ++k) out[k] = 0.0;
+    if (n == 0 || (P->m == 0 && !S->comm)) return VIPRS_OK;
+    HIP_TRY(hipSetDevice(P->device));
+    int rc = row_buffers(S, n);
+    if (rc != VIPRS_OK) return rc;
+    // (the sums staging is free: the previous reduction that read it has been collected)
+    SumsRow* h = sums_staging(S);
+    for (int i = 0; i < n; ++i) {
+        h[i] = sums_row(S, 0, P->m, cols ? cols[i] : i, 0.0, false, nullptr);
+        if (grid) h[i].nb = grid_sums_blocks(P->m);          // THE ORDER of a grid state's rows
+    }
+    rc = sums_enqueue(S, kSumsElasticNet, n, kNEnetSums, nullptr);
+    if (rc != VIPRS_OK) return rc;
+    std::vector<double> got((size_t)n * kNEnetSums);
+    rc = sums_collect(S, got.data(), "viprs_state_enet_sums");
+    if (rc != VIPRS_OK) return rc;
+    for (int i = 0; i < n; ++i) {                             // the maximum travels last, the header has it first
+        const double* g = got.data() + (size_t)i * kNEnetSums;
+        out[i * kNEnetSums] = g[kNEnetSums - 1];
+        for (int k = 1; k < kNEnetSums; ++k) out[i * kNEnetSums + k] = g[k - 1];
+    }
+    return VIPRS_OK;
 }
 
 int viprs_state_sums_columns_end(viprs_state* S, double* out) {

@@ -396,6 +396,19 @@ template <typename U> int launch_panel(viprs_plan* P, EStepArgs<float> A, int mo
 // band kernel for the windowed components
 template <typename U> int launch_band(viprs_plan* P, EStepArgs<float> A, int model);
 int band_ring_panels(const viprs_plan* P);
+// The two launchers behind their kernel selection (launch_panel.inc, launch_band.inc): everything but the choice of the
+// instantiation, which the caller hands in.  The elastic-net policy (panel_enet.h) is instantiated in translation units of
+// its own -- panel_enet_*.hip, band_enet_*.hip -- and launched through them: launch_panel_enet / launch_band_enet.
+#ifdef PANEL_NW
+constexpr int kPanelWaves = PANEL_NW;              // (experiments: kernels_common.h)
+#else
+constexpr int kPanelWaves = kClassWaves[0];
+#endif
+using BandKernelFn = void (*)(EStepArgs<float>, int);
+template <typename U> int launch_panel_kernel(viprs_plan* P, EStepArgs<float> A, int model, const void* kfn, int nw, int math_bit);
+template <typename U> int launch_band_kernel(viprs_plan* P, EStepArgs<float> A, BandKernelFn kfn, int math_bit);
+template <typename U> int launch_panel_enet(viprs_plan* P, EStepArgs<float> A);
+template <typename U> int launch_band_enet(viprs_plan* P, EStepArgs<float> A);
 // batched grid E-step on the matrix cores
 template <typename U> int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A);
 // LD product Y = dq_scale (R - diag) B (+ B) over every block of the plan (ld_dot.h); device pointers, (m, n_cols) column-major

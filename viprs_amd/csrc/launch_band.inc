@@ -9,22 +9,18 @@ namespace viprs {
 
 int band_ring_panels(const viprs_plan* P);
 
+// `kfn`: the estep_band_kernel instantiation of the model's policy for this form (the caller selects it: launch_band below;
+// launch_band_enet.inc for the policies that live in translation units of their own); `math_bit`: what it adds to
+// viprs_plan_last_math_modes.
 template <typename U>
-int launch_band(viprs_plan* P, EStepArgs<float> A, int model) {
+int launch_band_kernel(viprs_plan* P, EStepArgs<float> A, BandKernelFn kfn, int math_bit) {
     A.blocks = P->d_ragged.p;
     A.n_blocks = (int)P->ragged_h.size();
     A.counter = P->d_counters.p + 1;
     const int ring = band_ring_panels(P);
     const size_t shmem = (size_t)band_lds_floats(ring) * sizeof(float);
-    const bool exact = P->math_mode == VIPRS_MATH_EXACT;
-    P->math_used |= exact ? 1 : 2;
+    P->math_used |= math_bit;
     const bool upper = P->low_memory != 0;
-    void (*kfn)(EStepArgs<float>, int) = nullptr;
-#define BK(MODEL) (upper ? estep_band_kernel<U, MODEL, false> : estep_band_kernel<U, MODEL, true>)
-    if (model == kBandGridColumn) kfn = exact ? BK(GridColumnModel<true>) : BK(GridColumnModel<false>);
-    else if (model == kBandMixture) kfn = exact ? BK(MixtureSerialModel<true>) : BK(MixtureSerialModel<false>);
-    else kfn = exact ? BK(SpikeSlabModel<true>) : BK(SpikeSlabModel<false>);
-#undef BK
     HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     const int items = A.n_blocks * std::max(A.n_active, 1);
     const int grid = std::min(items, 2 * P->n_cu);
@@ -38,6 +34,20 @@ int launch_band(viprs_plan* P, EStepArgs<float> A, int model) {
     return VIPRS_OK;
 }
 
+template <typename U>
+int launch_band(viprs_plan* P, EStepArgs<float> A, int model) {
+    const bool exact = P->math_mode == VIPRS_MATH_EXACT;
+    const bool upper = P->low_memory != 0;
+    BandKernelFn kfn = nullptr;
+#define BK(MODEL) (upper ? estep_band_kernel<U, MODEL, false> : estep_band_kernel<U, MODEL, true>)
+    if (model == kBandGridColumn) kfn = exact ? BK(GridColumnModel<true>) : BK(GridColumnModel<false>);
+    else if (model == kBandMixture) kfn = exact ? BK(MixtureSerialModel<true>) : BK(MixtureSerialModel<false>);
+    else kfn = exact ? BK(SpikeSlabModel<true>) : BK(SpikeSlabModel<false>);
+#undef BK
+    return launch_band_kernel<U>(P, A, kfn, exact ? 1 : 2);
+}
+
+template int launch_band_kernel<BAND_U>(viprs_plan*, EStepArgs<float>, BandKernelFn, int);
 template int launch_band<BAND_U>(viprs_plan*, EStepArgs<float>, int);
 
 }  // namespace viprs

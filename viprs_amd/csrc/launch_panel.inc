@@ -11,10 +11,12 @@ namespace viprs {
 // large blocks first, small-block workers behind them (estep_panel.h); the second pass of the upper-triangular form
 // (update_q_factor, e_step.hpp:331-337) runs inside the sweep, over the mirrored blocks (kFormMirror), and so does the
 // bookkeeping that used to be two more launches (the prologue's zeroing, the commit of the team blocks' staged outputs).
-template <typename U, int NW>
-int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
+// `kfn`: the estep_sweep_kernel instantiation of the model's policy for this form, built for `nw` waves per workgroup and
+// panel_cols<U>() columns per updater lane (the caller selects it: launch_panel below; launch_panel_enet.inc for the
+// policies that live in translation units of their own); `math_bit`: what it adds to viprs_plan_last_math_modes.
+template <typename U>
+int launch_panel_kernel(viprs_plan* P, EStepArgs<float> A, int model, const void* kfn, int nw, int math_bit) {
     constexpr int CPL = panel_cols<U>();
-    const bool exact = P->math_mode == VIPRS_MATH_EXACT;
     const bool upper = P->low_memory != 0;
     // the arithmetic of the upper form runs over mirrored storage (kFormMirror): strips as in the symmetric form
     const bool mirror = upper;
@@ -22,17 +24,7 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
     const int n_models = std::max(1, A.n_active);
     const int* team_of = ((model == kPanelMixture || model == kPanelMixtureWide) && !sched_config().team_env) ? sched_config().class_team_mix
                                                                              : sched_config().class_team;
-    const void* kfn = nullptr;
-#define PK(MODEL) (upper ? (const void*)estep_sweep_kernel<U, MODEL, kFormMirror, NW, CPL>       \
-                          : (const void*)estep_sweep_kernel<U, MODEL, kFormSym, NW, CPL>)
-    // math_mode = fast: spike-and-slab, grid columns and mixtures of up to 8 components (wider mixtures stay exact)
-    if (model == kPanelGridColumn) kfn = exact ? PK(GridColumnModel<true>) : PK(GridColumnModel<false>);
-    else if (model == kPanelMixture) kfn = exact ? PK(MixtureModel<true>) : PK(MixtureModel<false>);
-    else if (model == kPanelMixtureWide) kfn = A.width <= 15 ? PK(MixtureWideModel<15>) : PK(MixtureWideModel<31>);
-    else kfn = exact ? PK(SpikeSlabModel<true>) : PK(SpikeSlabModel<false>);
-#undef PK
-    // (what this launch computes in: math_mode = fast has no wide-mixture instantiation -- viprs_plan_last_math_modes)
-    P->math_used |= (exact || model == kPanelMixtureWide) ? 1 : 2;
+    P->math_used |= math_bit;
 
     // hand-off granules (one set per model of a grid launch) and arrival counters of the team items; a launch generation
     // in the granule tags replaces their zeroing (20 bits: the buffer is cleared once every 2^20 launches)
@@ -113,7 +105,7 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
     if (shmem > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, NW * 64, shmem));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, nw * 64, shmem));
     per_cu = std::max(1, per_cu);
     if (const char* f = getenv("VIPRS_MAX_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(f)));   // experiments
     const int capacity = P->n_cu * per_cu;                  // every workgroup of the grid is resident at once
@@ -180,7 +172,7 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
     void* params[] = {(void*)&S};
     if (team_wgs > 0) { const int rc = team_launch_gate(P); if (rc != VIPRS_OK) return rc; }
     { const int rc = P->timing.launcher_start(); if (rc != VIPRS_OK) return rc; }      // (the sweep's start event: adjacent to the launch)
-    HIP_TRY(hipLaunchKernel(kfn, dim3(grid), dim3(NW * 64), params, shmem, P->stream));
+    HIP_TRY(hipLaunchKernel(kfn, dim3(grid), dim3(nw * 64), params, shmem, P->stream));
     if (team_wgs > 0) { const int rc = team_launch_done(P); if (rc != VIPRS_OK) return rc; }
     // (no commit launch: the member of a team that finishes a block last copies its staged eta / q into place)
     return VIPRS_OK;
@@ -192,13 +184,23 @@ int launch_panel_nw(viprs_plan* P, EStepArgs<float> A, int model) {
 // per step with 4 waves, tools/ab_bench.py.  -DPANEL_NW=n builds the other variant.)
 template <typename U>
 int launch_panel(viprs_plan* P, EStepArgs<float> A, int model) {
-#ifdef PANEL_NW
-    return launch_panel_nw<U, PANEL_NW>(P, A, model);
-#else
-    return launch_panel_nw<U, kClassWaves[0]>(P, A, model);
-#endif
+    constexpr int NW = kPanelWaves, CPL = panel_cols<U>();
+    const bool exact = P->math_mode == VIPRS_MATH_EXACT;
+    const bool upper = P->low_memory != 0;
+    const void* kfn = nullptr;
+#define PK(MODEL) (upper ? (const void*)estep_sweep_kernel<U, MODEL, kFormMirror, NW, CPL>       \
+                          : (const void*)estep_sweep_kernel<U, MODEL, kFormSym, NW, CPL>)
+    // math_mode = fast: spike-and-slab, grid columns and mixtures of up to 8 components (wider mixtures stay exact)
+    if (model == kPanelGridColumn) kfn = exact ? PK(GridColumnModel<true>) : PK(GridColumnModel<false>);
+    else if (model == kPanelMixture) kfn = exact ? PK(MixtureModel<true>) : PK(MixtureModel<false>);
+    else if (model == kPanelMixtureWide) kfn = A.width <= 15 ? PK(MixtureWideModel<15>) : PK(MixtureWideModel<31>);
+    else kfn = exact ? PK(SpikeSlabModel<true>) : PK(SpikeSlabModel<false>);
+#undef PK
+    // (what this launch computes in: math_mode = fast has no wide-mixture instantiation -- viprs_plan_last_math_modes)
+    return launch_panel_kernel<U>(P, A, model, kfn, NW, (exact || model == kPanelMixtureWide) ? 1 : 2);
 }
 
+template int launch_panel_kernel<PANEL_U>(viprs_plan*, EStepArgs<float>, int, const void*, int, int);
 template int launch_panel<PANEL_U>(viprs_plan*, EStepArgs<float>, int);
 
 #if defined(VIPRS_SWEEP_TRACE)

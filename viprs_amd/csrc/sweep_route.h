@@ -10,8 +10,8 @@ namespace viprs {
 // ---- kernel families (one translation unit per family and LD element type) and their model constants -------------
 enum { kFamNone = 0, kFamGeneric = 1, kFamTileF64 = 2, kFamPanel = 3, kFamBand = 4, kFamGridBatched = 5 };   // viprs_sweep_family
 enum { kGenSpikeSlab = 0, kGenMixture = 1, kGenGrid = 2 };          // = viprs_model_kind; the tile_f64 kernels take them too
-enum { kPanelSpikeSlab = 0, kPanelGridColumn = 1, kPanelMixture = 2, kPanelMixtureWide = 3 };
-enum { kBandSpikeSlab = 0, kBandGridColumn = 1, kBandMixture = 2 };
+enum { kPanelSpikeSlab = 0, kPanelGridColumn = 1, kPanelMixture = 2, kPanelMixtureWide = 3, kPanelElasticNet = 4 };
+enum { kBandSpikeSlab = 0, kBandGridColumn = 1, kBandMixture = 2, kBandElasticNet = 3 };
 
 // the launchers' own words for an LD element type they have no instantiation for
 constexpr const char* kDenseLdTypeError = "dense schedule with unsupported LD dtype";
@@ -49,5 +49,13 @@ struct SweepRoute {
 // VIPRS_OK, or VIPRS_EINVAL with the message the launch would give (`err`) when the chosen family has no instantiation for
 // the LD element type.
 int sweep_route(const SweepConfig& c, SweepRoute& r, std::string& err);
+
+// The route of an elastic-net sweep (viprs_state_enet_sweep) of an fp32 state of width 1 (`grid` false) or of a grid state:
+// the panel sweep for the dense blocks, the band kernel for the windowed ones -- the columns of a grid state as (block,
+// model) items, never the batched matrix-core kernel -- with the prologue and the events of the spike-and-slab row of
+// sweep_route for width 1 and of its grid row for a grid state.  There is no generic-kernel instantiation: windowed blocks
+// the band kernel cannot take (`band_ok` false) are VIPRS_EUNSUPPORTED; an LD element type outside fp32 / int8 / int16 is
+// VIPRS_EINVAL with the launcher's message, as above.
+int enet_route(bool grid, int ld_dtype, bool dense, bool ragged, bool band_ok, SweepRoute& r, std::string& err);
 
 }  // namespace viprs

@@ -852,6 +852,28 @@ class DeviceState:
         else:
             L.check(L.lib.viprs_state_e_step(self._h, float(dq_scale), None, 0, int(bool(sync))))
 
+    # -- elastic net (lassosum): coordinate descent on the sweep of the E-step ------------------------
+    def enet_sweep(self, dq_scale=1.0, active_model_idx=None, sync=True):
+        """One elastic-net sweep (`viprs_state_enet_sweep`, include/viprs_hip.h; `viprs_amd.stats.enet`) of a float32
+        spike-and-slab or grid state: ``mu_mult`` holds ``1 - s``, ``sqrt_half_var_tau`` / ``half_var_tau`` the penalty."""
+        active, n = None, 0
+        if active_model_idx is not None:
+            active = np.ascontiguousarray(active_model_idx, dtype=np.int32)
+            n = int(active.shape[0])
+        L.check(L.lib.viprs_state_enet_sweep(self._h, float(dq_scale), None if active is None else _ptr(active), n,
+                                             int(bool(sync))))
+
+    def enet_sums(self, cols=None):
+        """``(n, 6)`` float64, one row per listed column (default: every column): max |eta_diff|, sum std_beta eta,
+        sum q eta, sum eta^2, sum pen |eta|, the number of eta != 0 (`viprs_state_enet_sums`)."""
+        c = None if cols is None else np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32)
+        n = self.width if c is None else int(c.shape[0])
+        if self.model != "grid":
+            n = 1 if c is None else n
+        out = np.zeros((n, L.N_ENET_SUMS), dtype=np.float64)
+        L.check(L.lib.viprs_state_enet_sums(self._h, n, None if c is None else _ptr(c), _ptr(out)))
+        return out
+
     def dot(self, name="eta", dq_scale=1.0, include_diagonal=True):
         """``R @ eta`` with the resident posterior mean as `B` (`viprs_state_dot`): only the ``m x n_cols`` results cross to
         the host.  ``(m,)`` for spike-and-slab and mixture states, ``(m, G)`` column-major for grid states.  Any field other
