@@ -1,5 +1,6 @@
 """A/B of two builds of the library on the same box, alternating, kernel ms p50 of 30 sweeps each:
-    python tools/ab_bench.py LIB_A LIB_B [upper] [int8|int16] [grid|mix] [uniform]   (each library runs in its own subprocess, 3 rounds)"""
+    python tools/ab_bench.py LIB_A LIB_B [upper] [int8|int16] [grid|mix] [uniform] [fast]   (each library runs in its own subprocess, 3 rounds;
+    fast: math_mode="fast")"""
 import os, subprocess, sys
 args = [a for a in sys.argv[3:]]
 code = r'''
@@ -12,7 +13,7 @@ sizes = np.full(1700, 650) if "uniform" in sys.argv else None      # uniform: 17
 ld, ss, inp = syn.make_problem("cfg3", low_memory=upper, ld_dtype=dt, sizes=sizes)
 model = "grid" if "grid" in sys.argv else "mixture" if "mix" in sys.argv else "spike_slab"
 width = {"grid": 32, "mixture": 4, "spike_slab": 1}[model]
-plan = LDPlan(ld.ld_left_bound, ld.ld_indptr, ld.ld_data, upper); ds = DeviceState(plan, "float32", model, width)
+plan = LDPlan(ld.ld_left_bound, ld.ld_indptr, ld.ld_data, upper, math_mode="fast" if "fast" in sys.argv else "exact"); ds = DeviceState(plan, "float32", model, width)
 ds.upload("std_beta", inp.std_beta)
 active, pi0 = None, inp.pi
 if model == "spike_slab":
@@ -36,3 +37,5 @@ for rnd in range(3):
         env = dict(os.environ, VIPRS_HIP_LIB=os.path.abspath(lib))
         out = subprocess.run([sys.executable, "-c", code] + args, env=env, capture_output=True, text=True)
         print(rnd, name, os.path.basename(lib), out.stdout.strip() or out.stderr[-300:], flush=True)
+        if out.returncode != 0:         # a run that died: nothing more is started on the device
+            sys.exit(f"{os.path.basename(lib)} exited with {out.returncode}")

@@ -4,6 +4,9 @@
 # then, back in the authoring container:
 #   python profiles/summarize.py <tag> gpurun_out/<tag>_stats gpurun_out/<tag>_fetch gpurun_out/<tag>_write <traffic-key>
 # Counters are collected in their own passes (kernel-trace only), one PMC counter per pass.
+# VIPRS_HIP_LIB selects another build of the library (the parent's device code: tools/build_variant.sh NAME -DVIPRS_LD_STREAM=0).
+# A step that fails ends the collection: nothing more is started on the device after it.
+set -e
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 TAG=$1; shift

@@ -90,6 +90,28 @@ template <typename U> __host__ __device__ constexpr int panel_team_cols() {
 //  per-row running sums behind an LDS transposition; removed in round 6 after a round on the mirrored form.)
 constexpr int kFormSym = 1, kFormMirror = 2;
 
+// Cache policy of every LD load site of a role (panel_loads.h: kCached / kStream), in one place.  Each LD byte of a
+// block is used once per sweep by the workgroup that loads it -- except the tiles of a team block, which every member
+// stages for its own chain.
+//   strip       rows of a full panel under strip_update (both forms, every model, MIXED included).  16 bytes per lane
+//               cover whole 128-byte lines that nobody reads again: kStream.  The narrower strips (8 bytes per lane: int8
+//               LD, the int16 team strips of panel_team_cols; 4 bytes: the int8 team strips) stay kCached: streamed
+//               (VIPRS_LD_STREAM_NARROW) they gain nothing on the 3 619-SNP block's team.
+//   strip_tail  FULL = false, the partial last panel of a block: rows past its end are clamped to its last row and the
+//               same line is loaded up to 63 more times, which L1 serves: kCached (VIPRS_LD_STREAM_PARTIAL streams them:
+//               1 % slower on 1 700 blocks of 650 SNPs).
+//   tile        the first diagonal tile of a block and stage_tiles.  Queue role, fp32 / int16 (a tile row is a whole number
+//               of lines): read once by one workgroup, kStream.  A team's tiles are re-read by every member through L2 /
+//               Infinity Cache, and half of every line of an int8 tile row belongs to the neighbouring panel's tile: kCached.
+// Per-SNP inputs and outputs, the hand-off granules and stage_store keep their own (default / agent-scope) accesses.
+// -DVIPRS_LD_STREAM=0: kCached everywhere.  What was measured: EXPERIMENTS.md 6.27.
+template <typename U, int CPL, bool TEAM> struct PanelLdPolicy {
+    static constexpr bool kWide = CPL * sizeof(U) == 16;
+    static constexpr int strip = (VIPRS_LD_STREAM && (kWide || VIPRS_LD_STREAM_NARROW)) ? kStream : kCached;
+    static constexpr int strip_tail = (strip == kStream && VIPRS_LD_STREAM_PARTIAL) ? kStream : kCached;
+    static constexpr int tile = (VIPRS_LD_STREAM && !TEAM && sizeof(U) != 1) ? kStream : kCached;
+};
+
 template <typename U, typename MODEL, int FORM, int NW, bool TEAM, int CPL>
 __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int qcap, float* __restrict__ smem, const int wg) {
     // q[qcap] | a[2][64] | diagonal tiles[2][64 x 64] | off-diagonal tile[64 x 64] | mixture chain scratch.  For every
@@ -119,6 +141,7 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
 #else
     constexpr int kDepth = TEAM ? (kPanel / RawRow<U, CPL>::kWords < kPanel ? kPanel / RawRow<U, CPL>::kWords : kPanel) : kStripRowsInFlight;
 #endif
+    using LdPol = PanelLdPolicy<U, CPL, TEAM>;       // cache policy per LD load site
     __shared__ int s_blk;
     __shared__ int s_tdone;        // phases whose off-diagonal tile the chain has consumed (gate of the single lTo buffer)
     __shared__ int s_ddone;        // mirrored upper form: phases whose diagonal-tile sums are done (gate of the tile buffer they read)
@@ -213,7 +236,7 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
         // only ever meet a = 0)
         for (int i = tid; i < kPanel * kPanel / 4; i += NW * 64) {
             const int row = i >> 4, tcol = (i & 15) * 4;
-            *reinterpret_cast<float4*>(lT + row * kPanel + tcol) = load4<U>(base + (int64_t)min(row, b - 1) * stride + tcol);
+            *reinterpret_cast<float4*>(lT + row * kPanel + tcol) = load4<U, LdPol::tile>(base + (int64_t)min(row, b - 1) * stride + tcol);
         }
         __syncthreads();
 
@@ -636,7 +659,7 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
 #pragma unroll
                     for (int g = 0; g < kGroups; ++g) {
                         const int row = 4 * min(uw + g * (NW - 1), kPanel / 4 - 1) + trow;
-                        v[g] = load4<U>(base + (int64_t)min(row_base + row, b - 1) * stride + (p + 1) * kPanel + tcol);
+                        v[g] = load4<U, LdPol::tile>(base + (int64_t)min(row_base + row, b - 1) * stride + (p + 1) * kPanel + tcol);
                     }
                     float4 w[kGroups];
                     {
@@ -645,7 +668,7 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
 #pragma unroll
                         for (int g = 0; g < kGroups; ++g) {
                             const int row = 4 * min(uw + g * (NW - 1), kPanel / 4 - 1) + trow;
-                            w[g] = load4<U>(base + (int64_t)min(p * kPanel + row, b - 1) * stride + (p + 1) * kPanel + tcol);
+                            w[g] = load4<U, LdPol::tile>(base + (int64_t)min(p * kPanel + row, b - 1) * stride + (p + 1) * kPanel + tcol);
                         }
                     }
                     if (MIR && p > 0) {
@@ -726,9 +749,9 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                             const float fvec = left ? 1.0f : dq;
                             if (any_ed && active) {
                                 if (last_row == kPanel - 1)
-                                    strip_update<U, CPL, true, kDepth, true>(base + (int64_t)rr0 * stride + c, stride, last_row, edvec, tgt, fvec);
+                                    strip_update<U, CPL, true, kDepth, true, LdPol::strip>(base + (int64_t)rr0 * stride + c, stride, last_row, edvec, tgt, fvec);
                                 else
-                                    strip_update<U, CPL, false, kDepth, true>(base + (int64_t)rr0 * stride + c, stride, last_row, edvec, tgt, fvec);
+                                    strip_update<U, CPL, false, kDepth, true, LdPol::strip_tail>(base + (int64_t)rr0 * stride + c, stride, last_row, edvec, tgt, fvec);
                             }
                         } else {
                             // (pinned in a register under the full exec mask: strip_update reads it across lanes with v_readlane
@@ -738,9 +761,9 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                             asm volatile("" : "+v"(mvec));
                             if ((any_l ? any_ed : any_a) && active) {
                                 if (last_row == kPanel - 1)
-                                    strip_update<U, CPL, true, kDepth>(base + (int64_t)rr0 * stride + c, stride, last_row, mvec, tgt);
+                                    strip_update<U, CPL, true, kDepth, false, LdPol::strip>(base + (int64_t)rr0 * stride + c, stride, last_row, mvec, tgt);
                                 else
-                                    strip_update<U, CPL, false, kDepth>(base + (int64_t)rr0 * stride + c, stride, last_row, mvec, tgt);
+                                    strip_update<U, CPL, false, kDepth, false, LdPol::strip_tail>(base + (int64_t)rr0 * stride + c, stride, last_row, mvec, tgt);
                             }
                         }
                         if (k == uw) PPROF(6, wave == 1);
@@ -748,9 +771,9 @@ __device__ __forceinline__ void panel_role(const EStepArgs<float>& A0, const int
                     } else {
                         if (any_a && active) {
                             if (last_row == kPanel - 1)
-                                strip_update<U, CPL, true, kDepth>(base + (int64_t)rr0 * stride + c, stride, last_row, avec, lq_c);
+                                strip_update<U, CPL, true, kDepth, false, LdPol::strip>(base + (int64_t)rr0 * stride + c, stride, last_row, avec, lq_c);
                             else
-                                strip_update<U, CPL, false, kDepth>(base + (int64_t)rr0 * stride + c, stride, last_row, avec, lq_c);
+                                strip_update<U, CPL, false, kDepth, false, LdPol::strip_tail>(base + (int64_t)rr0 * stride + c, stride, last_row, avec, lq_c);
                         }
                         if (k == uw) PPROF(6, wave == 1);
                         hand_off();

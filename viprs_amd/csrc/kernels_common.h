@@ -15,6 +15,9 @@
     defined(PANEL_TEAM_STRIP_DEPTH) || \
     defined(PANEL_TEAM_CPL_F32) || \
     defined(PANEL_CHAIN_PRIO) || \
+    defined(VIPRS_LD_STREAM) || \
+    defined(VIPRS_LD_STREAM_PARTIAL) || \
+    defined(VIPRS_LD_STREAM_NARROW) || \
     defined(VIPRS_GRID_MFMA_CHAIN) || \
     defined(VIPRS_GRID_PROFILE) || \
     defined(VIPRS_TILE_PROFILE) || \
@@ -68,6 +71,21 @@
 #else
 #define VIPRS_BF_PANEL_CHAIN_PRIO ""
 #endif
+#ifdef VIPRS_LD_STREAM
+#define VIPRS_BF_VIPRS_LD_STREAM " VIPRS_LD_STREAM"
+#else
+#define VIPRS_BF_VIPRS_LD_STREAM ""
+#endif
+#ifdef VIPRS_LD_STREAM_PARTIAL
+#define VIPRS_BF_VIPRS_LD_STREAM_PARTIAL " VIPRS_LD_STREAM_PARTIAL"
+#else
+#define VIPRS_BF_VIPRS_LD_STREAM_PARTIAL ""
+#endif
+#ifdef VIPRS_LD_STREAM_NARROW
+#define VIPRS_BF_VIPRS_LD_STREAM_NARROW " VIPRS_LD_STREAM_NARROW"
+#else
+#define VIPRS_BF_VIPRS_LD_STREAM_NARROW ""
+#endif
 #ifdef VIPRS_GRID_MFMA_CHAIN
 #define VIPRS_BF_VIPRS_GRID_MFMA_CHAIN " VIPRS_GRID_MFMA_CHAIN"
 #else
@@ -93,7 +111,7 @@
 #else
 #define VIPRS_BF_VIPRS_PANEL_PROFILE ""
 #endif
-#define VIPRS_TU_BUILD_FLAGS VIPRS_BF_VIPRS_EXPERIMENTAL VIPRS_BF_PANEL_TIMING_NO_HANDOFF_WAIT VIPRS_BF_PANEL_TIMING_NO_SECOND_PASS VIPRS_BF_PANEL_NW VIPRS_BF_PANEL_STRIP_DEPTH VIPRS_BF_PANEL_MIN_WAVES VIPRS_BF_PANEL_TEAM_STRIP_DEPTH VIPRS_BF_PANEL_TEAM_CPL_F32 VIPRS_BF_PANEL_CHAIN_PRIO VIPRS_BF_VIPRS_GRID_MFMA_CHAIN VIPRS_BF_VIPRS_GRID_PROFILE VIPRS_BF_VIPRS_TILE_PROFILE VIPRS_BF_VIPRS_SWEEP_TRACE VIPRS_BF_VIPRS_PANEL_PROFILE
+#define VIPRS_TU_BUILD_FLAGS VIPRS_BF_VIPRS_EXPERIMENTAL VIPRS_BF_PANEL_TIMING_NO_HANDOFF_WAIT VIPRS_BF_PANEL_TIMING_NO_SECOND_PASS VIPRS_BF_PANEL_NW VIPRS_BF_PANEL_STRIP_DEPTH VIPRS_BF_PANEL_MIN_WAVES VIPRS_BF_PANEL_TEAM_STRIP_DEPTH VIPRS_BF_PANEL_TEAM_CPL_F32 VIPRS_BF_PANEL_CHAIN_PRIO VIPRS_BF_VIPRS_LD_STREAM VIPRS_BF_VIPRS_LD_STREAM_PARTIAL VIPRS_BF_VIPRS_LD_STREAM_NARROW VIPRS_BF_VIPRS_GRID_MFMA_CHAIN VIPRS_BF_VIPRS_GRID_PROFILE VIPRS_BF_VIPRS_TILE_PROFILE VIPRS_BF_VIPRS_SWEEP_TRACE VIPRS_BF_VIPRS_PANEL_PROFILE
 
 namespace viprs {
 // abi_plan.hip: the registry behind viprs_build_flags(); every translation unit with kernels registers its own string
