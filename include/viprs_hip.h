@@ -412,9 +412,9 @@ enum viprs_sweep_family {
     VIPRS_FAMILY_GENERIC = 1,        /* row-by-row kernels (called for an empty list too: they return at once) */
     VIPRS_FAMILY_TILE_F64 = 2,       /* float64 states: the panel-walking kernels (likewise) */
     VIPRS_FAMILY_PANEL = 3,          /* the panel sweep; model 0 spike-and-slab, 1 grid column, 2 mixture K <= 8, 3 mixture K <= 31
-                                        (4: the elastic net, viprs_enet_route only) */
+                                        (4: the elastic net, viprs_enet_route only; 5: the Gibbs draw, viprs_gibbs_route only) */
     VIPRS_FAMILY_BAND = 4,           /* band kernel of the windowed blocks; model 0 spike-and-slab, 1 grid column, 2 mixture
-                                        (3: the elastic net, viprs_enet_route only) */
+                                        (3: the elastic net, viprs_enet_route only; 4: the Gibbs draw, viprs_gibbs_route only) */
     VIPRS_FAMILY_GRID_BATCHED = 5    /* batched grid kernel on the matrix cores: one launch per 32 active columns, a 1-model
                                         prologue launch in front of every launch after the first */
 };
@@ -483,6 +483,71 @@ int viprs_sweep_route(int float_dtype, int model_kind, int width, int ld_dtype, 
 int viprs_state_enet_sweep(viprs_state* state, double dq_scale, const int32_t* active_model_idx, int n_active, int sync);
 int viprs_state_enet_sums(viprs_state* state, int n, const int32_t* cols, double* out);
 int viprs_enet_route(int grid, int ld_dtype, int dense, int ragged, int band_ok, int* route);
+
+/* ---- LDpred2: a Gibbs draw where the E-step takes an expectation ---------------------------------------------------------------
+ * LDpred2 (Prive, Arbel and Vilhjalmsson 2020; -grid and -auto) samples every effect from its conditional posterior under a
+ * point-normal prior (proportion p, heritability h2), SNP after SNP over each LD block with a running q = (R - I) beta.  With
+ * C1 = n_j h2 / (m p) its update of SNP j is C2 = C1 / (1 + C1), C3 = C2 (beta_hat_j - q_j), C4 = C2 / n_j,
+ * postp = 1 / (1 + (1-p)/p sqrt(1 + C1) exp(-C3^2 / (2 C4))), beta_j = postp > U ? C3 + z sqrt(C4) : 0: the grid-column E-step
+ * of viprs_state_e_step with sigma_epsilon = 1, lambda = 0 and tau_beta = m p / h2 -- under these viprs_state_prep_columns
+ * writes mu_mult = C2, half_var_tau = 1 / (2 C4) and u_logs = logit(p) - 0.5 log(1 + C1) -- with a draw stored in eta where the
+ * E-step stores gamma mu.  The reference has no such model; the definition is this library's own, stated in full.
+ * THE DRAWS.  viprs_state_gibbs_draws: for every SNP j of the plan and every listed column g one Philox4x32-10 block (Salmon
+ * et al. 2011; multipliers 0xD2511F53 and 0xCD9E8D57, Weyl increments 0x9E3779B9 and 0xBB67AE85, 10 rounds) with
+ *   key     = (low 32 bits of seed, high 32 bits of seed)
+ *   counter = (j, g, low 32 bits of draw_index, high 32 bits of draw_index)
+ * and from its output words x0, x1, x2, every operation separately rounded in float32:
+ *   U  = (2 (x0 >> 9) + 1) * 2^-24        exact in float32, strictly inside (0, 1); u1, u2 likewise from x1, x2
+ *   z  = sqrtf(-2 logf(u1)) * cospif(2 u2)
+ *   noise = z * (1.0f / sqrtf(2.0f * half_var_tau[j, g]))
+ * written to two (m, G) float32 buffers of the state (column-major like its fields), allocated by the first Gibbs call and
+ * freed with the state.  A draw depends on (seed, draw_index, j, g) alone, never on the launch, the other listed columns or
+ * the call that generated it.  logf / cospif are the device library's (a few ulp): U is bit-exact against a host
+ * implementation, noise is not (tests/test_gpu_gibbs.py states the bound).
+ * THE UPDATE.  Per SNP j in index order and per listed column, from the current q_j, every operation separately rounded in
+ * float32, no fused multiply-add, the sigmoid of e_step_grid (e_step.hpp:245-261, :599-635) with glibc's expf:
+ *   mu    = fl(mu_mult_j * fl(std_beta_j - q_j))
+ *   gamma = sigmoid(fl(u_logs_j + fl(fl(half_var_tau_j * mu) * mu)))
+ *   b     = gamma > U_j ? fl(mu + noise_j) : +0                   (strict: gamma == U_j leaves the SNP out)
+ *   d     = fl(b - eta_old_j)
+ *   var_mu[j] = mu;  var_gamma[j] = gamma;  eta_diff[j] = d;  eta[j] = b
+ * then the E-step's own update of q over the row's window, q[k] = fma(R[j,k], dq_scale * d, q[k]) (symmetric form: followed by
+ * q[j] -= d), and after the block the second pass of the upper form, as for viprs_state_enet_sweep.  There is no skip branch.
+ *   viprs_state_gibbs_sweep   the draws for the listed columns (unless VIPRS_GIBBS_KEEP_DRAWS is set in `flags`: then the
+ *                             sweep uses whatever the two buffers hold), then one sweep over every LD block the plan's sweeps
+ *                             visit, on an fp32 state of kind VIPRS_MODEL_GRID, width >= 1; `active_model_idx` / `n_active` as
+ *                             in viprs_state_e_step (distinct columns; NULL: every column); asynchronous on the plan's stream
+ *                             unless `sync` != 0.  The exact arithmetic whatever the plan's math_mode.
+ * KERNELS.  The panel sweep serves the dense blocks (model 5) and the band kernel the windowed ones (model 4), for fp32, int8
+ * and int16 LD in both forms; the columns run as (block, model) items of ONE panel launch, never on the batched matrix-core
+ * kernel.  Sweep timing goes through the plan's timing record (viprs_plan_last_kernel_ms: the draws kernel is outside it);
+ * viprs_plan_last_gibbs_draws_ms is the event time of the last draws kernel.
+ * REFUSALS, each VIPRS_EINVAL before any launch: a float64 state; a spike-and-slab-kind or mixture state; a grid state under a
+ * (group, column) mask; windowed blocks the band kernel cannot take (VIPRS_BAND=0, or a window wider than its q ring);
+ * VIPRS_GIBBS_KEEP_DRAWS before the draw buffers exist (no draws call, sweep or upload yet).
+ *   viprs_gibbs_route         the route of such a sweep (pure host code; usable without a GPU): dense blocks VIPRS_FAMILY_PANEL
+ *                             with model 5, windowed blocks VIPRS_FAMILY_BAND with model 4, prologue and events as the grid row
+ *                             of viprs_sweep_route, whose arguments and answers are unchanged
+ *   viprs_state_gibbs_upload / _download   one of the state's Gibbs buffers, `which` a viprs_gibbs_buffer: (m, G) column-major,
+ *                             float32 (UNIF, NOISE) or float64 (MEAN_SUM); a buffer that does not exist yet is created, zeroed
+ *   viprs_state_gibbs_accumulate   mean_sum[j, g] += (double)var_gamma[j, g] * (double)var_mu[j, g] for the listed (distinct)
+ *                             columns: the Rao-Blackwellised posterior mean of the draw, summed over sweeps.  Synchronous
+ *   viprs_state_gibbs_reset_mean   zeroes mean_sum
+ * The per-sweep scalars a sampler needs -- the number of eta != 0, sum q eta, sum eta^2, sum std_beta eta -- are columns
+ * [5], [2], [3], [1] of viprs_state_enet_sums.
+ * NOT BUILT: LDpred2's `sparse` option; allow_jump_sign / use_MLE / shrink_corr of later bigsnpr versions; float64 and
+ * mixture states; several ranks; a math_mode = fast variant. */
+enum viprs_gibbs_buffer { VIPRS_GIBBS_UNIF = 0, VIPRS_GIBBS_NOISE = 1, VIPRS_GIBBS_MEAN_SUM = 2, VIPRS_GIBBS_BUFFER_COUNT = 3 };
+#define VIPRS_GIBBS_KEEP_DRAWS 1
+int viprs_state_gibbs_draws(viprs_state* state, uint64_t seed, uint64_t draw_index, const int32_t* active_model_idx, int n_active);
+int viprs_state_gibbs_sweep(viprs_state* state, double dq_scale, const int32_t* active_model_idx, int n_active, uint64_t seed,
+                            uint64_t draw_index, int flags, int sync);
+int viprs_state_gibbs_upload(viprs_state* state, int which, const void* host);
+int viprs_state_gibbs_download(viprs_state* state, int which, void* host);
+int viprs_state_gibbs_accumulate(viprs_state* state, const int32_t* active_model_idx, int n_active);
+int viprs_state_gibbs_reset_mean(viprs_state* state);
+int viprs_gibbs_route(int ld_dtype, int dense, int ragged, int band_ok, int* route);
+int viprs_plan_last_gibbs_draws_ms(viprs_plan* plan, double* ms);
 
 /* ---- LD product: Y = R B over EVERY block of a plan -------------------------------------------------------------------
  * What the reference computes with `ld.dot(B)`: the pseudo-validation metrics against a validation LD panel

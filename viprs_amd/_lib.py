@@ -32,6 +32,9 @@ N_SUMS = 11
 N_ENET_SUMS = 6
 FIELD_ENET_MULT, FIELD_ENET_PENALTY = FIELD_MU_MULT, FIELD_SQRT_HALF_VAR_TAU
 PANEL_ELASTIC_NET, BAND_ELASTIC_NET = 4, 3          # model constants of the elastic-net route (viprs_enet_route)
+PANEL_GIBBS, BAND_GIBBS = 5, 4                      # ... of the Gibbs route (viprs_gibbs_route)
+GIBBS_UNIF, GIBBS_NOISE, GIBBS_MEAN_SUM = 0, 1, 2   # viprs_gibbs_buffer
+GIBBS_KEEP_DRAWS = 1
 COMM_ID_BYTES = 128
 
 
@@ -53,6 +56,7 @@ lib = ctypes.CDLL(LIB_PATH)
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
+_u64 = ctypes.c_uint64
 _d = ctypes.c_double
 _pi64 = ctypes.POINTER(ctypes.c_int64)
 _pi32 = ctypes.POINTER(ctypes.c_int32)
@@ -132,6 +136,14 @@ _PROTOS = {
     "viprs_state_enet_sweep": (_i, [_vp, _d, _vp, _i, _i]),
     "viprs_state_enet_sums": (_i, [_vp, _i, _vp, _vp]),
     "viprs_enet_route": (_i, [_i] * 5 + [ctypes.POINTER(_i)]),
+    "viprs_state_gibbs_draws": (_i, [_vp, _u64, _u64, _vp, _i]),
+    "viprs_state_gibbs_sweep": (_i, [_vp, _d, _vp, _i, _u64, _u64, _i, _i]),
+    "viprs_state_gibbs_upload": (_i, [_vp, _i, _vp]),
+    "viprs_state_gibbs_download": (_i, [_vp, _i, _vp]),
+    "viprs_state_gibbs_accumulate": (_i, [_vp, _vp, _i]),
+    "viprs_state_gibbs_reset_mean": (_i, [_vp]),
+    "viprs_gibbs_route": (_i, [_i] * 4 + [ctypes.POINTER(_i)]),
+    "viprs_plan_last_gibbs_draws_ms": (_i, [_vp, ctypes.POINTER(_d)]),
     "viprs_plan_dot": (_i, [_vp, _i, _i, _vp, _vp, _d, _i]),
     "viprs_state_dot": (_i, [_vp, _i, _d, _i, _vp]),
     "viprs_plan_last_dot_ms": (_i, [_vp, ctypes.POINTER(_d)]),
@@ -209,4 +221,11 @@ def enet_route(grid, ld_dtype, dense, ragged, band_ok=True):
     """The route of an elastic-net sweep (`viprs_enet_route`, include/viprs_hip.h) as a dict over ROUTE_FIELDS; needs no GPU."""
     out = (_i * len(ROUTE_FIELDS))()
     check(lib.viprs_enet_route(int(bool(grid)), ld_dtype, int(dense), int(ragged), int(band_ok), out))
+    return dict(zip(ROUTE_FIELDS, out))
+
+
+def gibbs_route(ld_dtype, dense, ragged, band_ok=True):
+    """The route of an LDpred2 Gibbs sweep (`viprs_gibbs_route`, include/viprs_hip.h) as a dict over ROUTE_FIELDS; needs no GPU."""
+    out = (_i * len(ROUTE_FIELDS))()
+    check(lib.viprs_gibbs_route(ld_dtype, int(dense), int(ragged), int(band_ok), out))
     return dict(zip(ROUTE_FIELDS, out))

@@ -122,13 +122,18 @@ int launch_family(viprs_state* S, const EStepArgs<T>& A, int family, int model, 
                 return launch_tile_f64<decltype(u)>(P, A, model, dense); });
     } else {
         // (kPanelGridColumn: ONE launch over (block, model) work items, select_model offsets the columns in-kernel)
-        // (the elastic-net policy has its own translation units and launchers: launch_panel_enet.inc, launch_band_enet.inc)
+        // (the elastic-net and Gibbs policies have their own translation units and launchers: launch_panel_enet.inc,
+        //  launch_band_enet.inc, launch_panel_gibbs.inc, launch_band_gibbs.inc)
         if (family == kFamPanel)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
-                return model == kPanelElasticNet ? launch_panel_enet<decltype(u)>(P, A) : launch_panel<decltype(u)>(P, A, model); });
+                return model == kPanelElasticNet ? launch_panel_enet<decltype(u)>(P, A)
+                       : model == kPanelGibbs    ? launch_panel_gibbs<decltype(u)>(P, A)
+                                                 : launch_panel<decltype(u)>(P, A, model); });
         if (family == kFamBand)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kBandLdTypeError, [&](auto u) {
-                return model == kBandElasticNet ? launch_band_enet<decltype(u)>(P, A) : launch_band<decltype(u)>(P, A, model); });
+                return model == kBandElasticNet ? launch_band_enet<decltype(u)>(P, A)
+                       : model == kBandGibbs    ? launch_band_gibbs<decltype(u)>(P, A)
+                                                : launch_band<decltype(u)>(P, A, model); });
         if (family == kFamGridBatched)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
                 return launch_grid_chunks<decltype(u)>(S, A); });
@@ -143,6 +148,9 @@ int launch_route(viprs_state* S, const SweepRoute& r, double dq, const int32_t* 
     EStepArgs<T> A = make_args<T>(S, dq);
     A.active = d_active;
     A.n_active = n_active;
+    // a Gibbs sweep: the slot a grid state does not use carries its draws (panel_gibbs.h)
+    if constexpr (std::is_same<T, float>::value)
+        if (r.dense_model == kPanelGibbs || r.ragged_model == kBandGibbs) A.log_null_pi = gibbs_draws_slot(S);
     if (S->model_kind == VIPRS_MODEL_GRID && !S->group_cols_h.empty()) {     // (group_mask_prepare: fp32 state, dense blocks only)
         A.blk_group = S->d_blk_group.p;
         A.group_cols = S->d_group_cols.p;
@@ -343,6 +351,52 @@ int viprs_enet_route(int grid, int ld_dtype, int dense, int ragged, int band_ok,
     SweepRoute r;
     std::string err;
     const int rc = enet_route(grid != 0, ld_dtype, dense != 0, ragged != 0, band_ok != 0, r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    route_fields(r, route);
+    return VIPRS_OK;
+}
+
+int viprs_state_gibbs_sweep(viprs_state* S, double dq_scale, const int32_t* active, int n_active, uint64_t seed,
+                            uint64_t draw_index, int flags, int sync) {
+    if (!S) return fail(VIPRS_EINVAL, "null state");
+    // every refusal comes before the first launch
+    if (S->model_kind != VIPRS_MODEL_GRID)
+        return fail(VIPRS_EINVAL, "Gibbs sweep: a state of kind VIPRS_MODEL_GRID is needed (spike-and-slab-kind and mixture "
+                                  "states are refused)");
+    if (S->float_dtype != VIPRS_F32) return fail(VIPRS_EINVAL, "Gibbs sweep: float64 states are not supported (the kernels are float32)");
+    if (!S->group_cols_h.empty()) return fail(VIPRS_EINVAL, "Gibbs sweep: a grid state under a (group, column) mask is not supported");
+    if (flags & ~VIPRS_GIBBS_KEEP_DRAWS) return fail(VIPRS_EINVAL, "Gibbs sweep: unknown flag");
+    const bool keep = (flags & VIPRS_GIBBS_KEEP_DRAWS) != 0;
+    viprs_plan* P = S->plan;
+    if (keep && !S->d_gibbs_draws.p && P->m > 0)
+        return fail(VIPRS_EINVAL, "Gibbs sweep: VIPRS_GIBBS_KEEP_DRAWS before the draw buffers exist (no draws call, sweep or "
+                                  "upload yet)");
+    std::vector<int32_t> all;
+    int rc = active_list_check(S, active, n_active, all);
+    if (rc != VIPRS_OK) return rc;
+    SweepRoute r;
+    std::string err;
+    rc = gibbs_route(P->ld_dtype, !P->dense_h.empty(), !P->ragged_h.empty(), band_ok(P), r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    if (n_active == 0 || P->m == 0) return VIPRS_OK;
+    HIP_TRY(hipSetDevice(P->device));
+    rc = active_list_upload(S, active, n_active);
+    if (rc != VIPRS_OK) return rc;
+    if (!keep) {
+        rc = gibbs_enqueue_draws(S, seed, draw_index, S->d_active.p, n_active);
+        if (rc != VIPRS_OK) return rc;
+    }
+    rc = run_route(S, r, dq_scale, S->d_active.p, n_active);
+    if (rc != VIPRS_OK) return rc;
+    if (sync) HIP_TRY(hipStreamSynchronize(P->stream));
+    return VIPRS_OK;
+}
+
+int viprs_gibbs_route(int ld_dtype, int dense, int ragged, int band_ok, int* route) {
+    if (!route) return fail(VIPRS_EINVAL, "null argument");
+    SweepRoute r;
+    std::string err;
+    const int rc = gibbs_route(ld_dtype, dense != 0, ragged != 0, band_ok != 0, r, err);
     if (rc != VIPRS_OK) return fail(rc, err);
     route_fields(r, route);
     return VIPRS_OK;

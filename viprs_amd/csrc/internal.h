@@ -293,6 +293,7 @@ struct viprs_plan {
     viprs::EventBracket time_clump;
     viprs::DevBuf<viprs::RidgeBlock> d_solver_blocks;   // start and size of every LD block, SNP order (ensure_solver_blocks)
     viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
+    viprs::EventBracket time_gibbs_draws;          // the draws kernel of the Gibbs sweeps (abi_gibbs.hip)
     viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
 
     ~viprs_plan();
@@ -333,6 +334,10 @@ struct viprs_state {
     size_t sums_total = 0;                  // doubles of the reduction in flight (or of the zeros `end` returns: sums_empty)
     bool sums_pending = false, sums_empty = false;
     viprs_comm* comm = nullptr;             // viprs_state_set_comm: the sums are all-rank sums (one all-gather per reduction)
+    // LDpred2 Gibbs sweeps (abi_gibbs.hip), allocated by the first Gibbs call: 2 x (m, G) float32 -- U, then noise -- and the
+    // (m, G) float64 sum of the Rao-Blackwellised means
+    viprs::DevBuf<float> d_gibbs_draws;
+    viprs::DevBuf<double> d_gibbs_mean;
     ~viprs_state() {
         if (h_sums) (void)hipHostFree(h_sums);
         if (h_rows) (void)hipHostFree(h_rows);
@@ -409,6 +414,16 @@ template <typename U> int launch_panel_kernel(viprs_plan* P, EStepArgs<float> A,
 template <typename U> int launch_band_kernel(viprs_plan* P, EStepArgs<float> A, BandKernelFn kfn, int math_bit);
 template <typename U> int launch_panel_enet(viprs_plan* P, EStepArgs<float> A);
 template <typename U> int launch_band_enet(viprs_plan* P, EStepArgs<float> A);
+// the LDpred2 Gibbs policy (panel_gibbs.h) likewise: panel_gibbs_*.hip, band_gibbs_*.hip
+template <typename U> int launch_panel_gibbs(viprs_plan* P, EStepArgs<float> A);
+template <typename U> int launch_band_gibbs(viprs_plan* P, EStepArgs<float> A);
+// abi_gibbs.hip: the state's draw buffers (U, then noise: the two halves of ONE allocation, created by the first Gibbs call),
+// the draws kernel on the plan's stream between the plan's own two events (device list of columns; nothing is synchronised),
+// and what a Gibbs sweep hands the policy in the log_null_pi slot of its arguments (panel_gibbs.h): the distance in bytes
+// from the state's mu_mult buffer to U
+int gibbs_ensure_draws(viprs_state* S);
+int gibbs_enqueue_draws(viprs_state* S, uint64_t seed, uint64_t draw_index, const int32_t* d_active, int n_active);
+const float* gibbs_draws_slot(const viprs_state* S);
 // batched grid E-step on the matrix cores
 template <typename U> int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A);
 // LD product Y = dq_scale (R - diag) B (+ B) over every block of the plan (ld_dot.h); device pointers, (m, n_cols) column-major

@@ -10,8 +10,8 @@ namespace viprs {
 // ---- kernel families (one translation unit per family and LD element type) and their model constants -------------
 enum { kFamNone = 0, kFamGeneric = 1, kFamTileF64 = 2, kFamPanel = 3, kFamBand = 4, kFamGridBatched = 5 };   // viprs_sweep_family
 enum { kGenSpikeSlab = 0, kGenMixture = 1, kGenGrid = 2 };          // = viprs_model_kind; the tile_f64 kernels take them too
-enum { kPanelSpikeSlab = 0, kPanelGridColumn = 1, kPanelMixture = 2, kPanelMixtureWide = 3, kPanelElasticNet = 4 };
-enum { kBandSpikeSlab = 0, kBandGridColumn = 1, kBandMixture = 2, kBandElasticNet = 3 };
+enum { kPanelSpikeSlab = 0, kPanelGridColumn = 1, kPanelMixture = 2, kPanelMixtureWide = 3, kPanelElasticNet = 4, kPanelGibbs = 5 };
+enum { kBandSpikeSlab = 0, kBandGridColumn = 1, kBandMixture = 2, kBandElasticNet = 3, kBandGibbs = 4 };
 
 // the launchers' own words for an LD element type they have no instantiation for
 constexpr const char* kDenseLdTypeError = "dense schedule with unsupported LD dtype";
@@ -57,5 +57,10 @@ int sweep_route(const SweepConfig& c, SweepRoute& r, std::string& err);
 // the band kernel cannot take (`band_ok` false) are VIPRS_EUNSUPPORTED; an LD element type outside fp32 / int8 / int16 is
 // VIPRS_EINVAL with the launcher's message, as above.
 int enet_route(bool grid, int ld_dtype, bool dense, bool ragged, bool band_ok, SweepRoute& r, std::string& err);
+
+// The route of an LDpred2 Gibbs sweep (viprs_state_gibbs_sweep) of an fp32 grid state: kPanelGibbs for the dense blocks,
+// kBandGibbs for the windowed ones, the columns as (block, model) items, with the prologue and the events of the grid row of
+// sweep_route.  Refusals as enet_route's, in its own words.
+int gibbs_route(int ld_dtype, bool dense, bool ragged, bool band_ok, SweepRoute& r, std::string& err);
 
 }  // namespace viprs

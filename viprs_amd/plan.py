@@ -375,6 +375,12 @@ class LDPlan:
                                        _ptr(out)))
         return out[:, 0] if scalar else out
 
+    def last_gibbs_draws_ms(self):
+        """Event time (ms) of the last Gibbs draws kernel on this plan (`viprs_plan_last_gibbs_draws_ms`)."""
+        ms = ctypes.c_double()
+        L.check(L.lib.viprs_plan_last_gibbs_draws_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     def last_clump_ms(self):
         """HIP-event time (ms) of the kernels of the last `clump` on this plan."""
         ms = ctypes.c_double(0.0)
@@ -873,6 +879,52 @@ class DeviceState:
         out = np.zeros((n, L.N_ENET_SUMS), dtype=np.float64)
         L.check(L.lib.viprs_state_enet_sums(self._h, n, None if c is None else _ptr(c), _ptr(out)))
         return out
+
+    # -- LDpred2: a Gibbs draw where the E-step takes an expectation ------------------------------------
+    _GIBBS = {"unif": (L.GIBBS_UNIF, np.float32), "noise": (L.GIBBS_NOISE, np.float32), "mean_sum": (L.GIBBS_MEAN_SUM, np.float64)}
+
+    @staticmethod
+    def _active(active_model_idx):
+        if active_model_idx is None:
+            return None, 0
+        a = np.ascontiguousarray(active_model_idx, dtype=np.int32)
+        return a, int(a.shape[0])
+
+    def gibbs_draws(self, seed, draw_index, active_model_idx=None):
+        """The draws of the listed columns (default: every column) of a float32 grid state (`viprs_state_gibbs_draws`,
+        include/viprs_hip.h; `viprs_amd.stats.gibbs.gibbs_draws_host`): a function of (seed, draw_index, SNP, column)."""
+        a, n = self._active(active_model_idx)
+        L.check(L.lib.viprs_state_gibbs_draws(self._h, int(seed), int(draw_index), None if a is None else _ptr(a), n))
+
+    def gibbs_sweep(self, dq_scale=1.0, active_model_idx=None, seed=0, draw_index=0, keep_draws=False, sync=True):
+        """One LDpred2 Gibbs sweep (`viprs_state_gibbs_sweep`; `viprs_amd.stats.gibbs`) of a float32 grid state prepared by
+        `prep_columns` with sigma_epsilon = 1, lambda = 0, tau_beta = m p / h2: fresh draws for the listed columns, or --
+        `keep_draws` -- whatever the two buffers hold."""
+        a, n = self._active(active_model_idx)
+        L.check(L.lib.viprs_state_gibbs_sweep(self._h, float(dq_scale), None if a is None else _ptr(a), n, int(seed),
+                                              int(draw_index), L.GIBBS_KEEP_DRAWS if keep_draws else 0, int(bool(sync))))
+
+    def gibbs_accumulate(self, active_model_idx=None):
+        """``mean_sum += float64(var_gamma) * float64(var_mu)`` for the listed columns (`viprs_state_gibbs_accumulate`)."""
+        a, n = self._active(active_model_idx)
+        L.check(L.lib.viprs_state_gibbs_accumulate(self._h, None if a is None else _ptr(a), n))
+
+    def gibbs_reset_mean(self):
+        L.check(L.lib.viprs_state_gibbs_reset_mean(self._h))
+
+    def gibbs_download(self, which):
+        """``"unif"`` / ``"noise"`` (float32) or ``"mean_sum"`` (float64), ``(m, G)`` column-major."""
+        code, dt = self._GIBBS[which]
+        out = np.zeros((self.plan.m, self.width), dtype=dt, order="F")
+        L.check(L.lib.viprs_state_gibbs_download(self._h, code, _ptr(out)))
+        return out
+
+    def gibbs_upload(self, which, array):
+        code, dt = self._GIBBS[which]
+        a = np.asarray(array)
+        if a.dtype != dt or a.shape != (self.plan.m, self.width) or not a.flags.f_contiguous:
+            raise ValueError(f"{which}: a Fortran-contiguous {np.dtype(dt).name} array of shape {(self.plan.m, self.width)}")
+        L.check(L.lib.viprs_state_gibbs_upload(self._h, code, _ptr(a)))
 
     def dot(self, name="eta", dq_scale=1.0, include_diagonal=True):
         """``R @ eta`` with the resident posterior mean as `B` (`viprs_state_dot`): only the ``m x n_cols`` results cross to
