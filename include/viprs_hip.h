@@ -549,6 +549,79 @@ int viprs_state_gibbs_reset_mean(viprs_state* state);
 int viprs_gibbs_route(int ld_dtype, int dense, int ragged, int band_ok, int* route);
 int viprs_plan_last_gibbs_draws_ms(viprs_plan* plan, double* ms);
 
+/* ---- PRS-CS: continuous-shrinkage Gibbs on the sweep of LDpred2 ----------------------------------------------------------------
+ * PRS-CS (Ge et al. 2019) puts the prior beta_j ~ N(0, sigma2 / n * psi_j) on every effect, psi_j ~ Gamma(a, delta_j),
+ * delta_j ~ Gamma(b, phi).  Given the other effects the conditional of beta_j is Gaussian with mean
+ * psi_j / (1 + psi_j) (beta_hat_j - q_j) and variance sigma2 / (n_j (1 + 1 / psi_j)): what viprs_state_gibbs_sweep draws from
+ * mu_mult = psi / (1 + psi), half_var_tau = n_j (1 + 1 / psi) / (2 sigma2) and u_logs = 32 -- the exact sigmoid of x >= 32 is
+ * 1.0f in float32 and U < 1, so every SNP is drawn and var_gamma == 1.  The sweep, its kernels and its route are those of the
+ * LDpred2 section, untouched.  The calls below are the other half of the sampler: after every sweep a new local scale psi for
+ * each (SNP, chain) and the three E-step inputs rewritten from it.  For a = 1, b = 1/2 the draws have closed forms with a
+ * fixed number of variates: delta ~ Gamma(3/2) / (psi + phi) with Gamma(3/2) = z^2 / 2 + Exp(1), and psi ~ GIG(1/2, 2 delta,
+ * n beta^2 / sigma2), whose reciprocal is inverse-Gaussian (Michael, Schucany and Haas 1976: one normal, one uniform, no
+ * rejection loop), written in s = sqrt(b_gig / a_gig) so that beta = 0 needs no special case.  The reference has no such
+ * model; the definition is this library's own, stated in full.  All calls: fp32 states of kind VIPRS_MODEL_GRID, one chain per
+ * column, `n_j` from viprs_state_set_n_per_snp, lists of DISTINCT columns (NULL: every column).
+ * BUFFERS.  Six (m, G) float32 arrays (viprs_cs_buffer; column-major like the fields) in one allocation of the state, made by
+ * the first cs call with psi = 1 and the rest zero, freed with the state.  States that never make a cs call do not grow.
+ * THE VARIATES.  viprs_state_cs_variates: for every SNP j and every listed column g one Philox4x32-10 block with the constants
+ * and the key of viprs_state_gibbs_draws and
+ *   counter = (j, g + 2^31, low 32 bits of draw_index, high 32 bits of draw_index)
+ * (the tag bit keeps the stream disjoint from the Gibbs draws of the same seed and draw_index), and from its output words
+ * x0 .. x3, every operation separately rounded in float32:
+ *   ub = (2 (x0 >> 9) + 1) * 2^-24;  u1, u2, u3 likewise from x1, x2, x3
+ *   r  = sqrtf(-2 logf(u1))
+ *   z1 = r * cospif(2 u2);  z2 = r * sinpif(2 u2)
+ *   e  = -logf(u3)
+ * written to VIPRS_CS_UB, _Z1, _Z2, _E.  A variate depends on (seed, draw_index, j, g) alone.  ub is bit-exact against a host
+ * implementation; z1, z2 and e carry the device library's logf / cospif / sinpif (tests/test_gpu_cs.py states the bounds).
+ * THE UPDATE.  viprs_state_cs_update, `params`: n rows (column, sigma2, phi).  Per SNP j and listed column, in float64, every
+ * operation separately rounded, no fused multiply-add, from the stored float32 variates, psi_old = VIPRS_CS_PSI[j, g] and
+ * eta = VIPRS_FIELD_ETA[j, g]:
+ *   g15   = 0.5 z2 z2 + e
+ *   delta = g15 / (psi_old + phi)
+ *   lam   = 2 delta
+ *   s     = |eta| sqrt(n_j / (lam sigma2))
+ *   y     = z1 z1
+ *   A     = s + (y + sqrt(y (4 lam s + y))) / (2 lam)
+ *   psi   = (ub (A + s) <= A) ? A : s s / A
+ *   psi   = psi < 2^-40 ? 2^-40 : psi;  psi = psi > psi_max ? psi_max : psi          (comparisons: a NaN stays a NaN)
+ *   psi32 = (float)psi;  delta32 = (float)delta;  p = (double)psi32
+ *   mu_mult = (float)(p / (1 + p));  half_var_tau = (float)(n_j (1 + 1 / p) / (2 sigma2));  u_logs = 32.0f
+ * products associate from the left.  It writes VIPRS_CS_PSI, VIPRS_CS_DELTA and the three fields of the listed columns; other
+ * columns keep their bits, buffers and fields alike.  The variates kernel runs first with (seed, draw_index) unless
+ * VIPRS_CS_KEEP_VARIATES is set: then the update uses what the buffers hold.  VIPRS_CS_PREPARE_ONLY draws nothing and reads no
+ * variate: it rewrites the three fields from the stored psi and the given sigma2 (phi is checked, not used) -- the start of a
+ * chain, and the way to change sigma2 alone.  Asynchronous on the plan's stream unless `sync` != 0.  Both kernels are
+ * grid-stride walks over the n x m rectangle without LDS or atomics.
+ * THE SUMS.  viprs_state_cs_sums, `out`: n rows of VIPRS_N_CS_SUMS doubles, one per listed column (`cols` NULL: columns
+ * 0 .. n - 1 with n = the state's width):
+ *   [0] sum eta^2 / psi   [1] sum n_j eta^2 / psi   [2] sum delta   [3] sum psi
+ * terms formed in double from the float32 values, t = (double)eta * (double)eta / (double)psi, then n_j * t, summed in THE
+ * ORDER defined above for the rows of a grid state (cap 256 workgroups), as viprs_state_enet_sums.  Synchronous.
+ * REFUSALS, each VIPRS_EINVAL before any launch, outputs untouched: a float64 state; a spike-and-slab-kind or mixture state; a
+ * grid state under a (group, column) mask; a state with a communicator (viprs_state_set_comm: several ranks are not built);
+ * update and sums without viprs_state_set_n_per_snp; a column out of range or listed twice; sigma2 or phi not positive and
+ * finite; psi_max outside (2^-40, inf); an unknown flag; VIPRS_CS_KEEP_VARIATES before the buffers exist; null pointers.  A
+ * plan without SNPs returns VIPRS_OK.
+ *   viprs_state_cs_upload / _download   one of the six buffers, `which` a viprs_cs_buffer (created if need be)
+ *   viprs_plan_last_cs_ms     the event times of the last variates kernel and of the last update kernel (0 for one that has
+ *                             not run; VIPRS_EINVAL when neither has)
+ * NOT BUILT: a != 1 or b != 1/2; the joint draw of an LD block through its Cholesky factor (the single-site chain has the same
+ * stationary distribution); float64 and mixture states; several ranks; a math_mode = fast variant. */
+enum viprs_cs_buffer { VIPRS_CS_PSI = 0, VIPRS_CS_DELTA = 1, VIPRS_CS_UB = 2, VIPRS_CS_Z1 = 3, VIPRS_CS_Z2 = 4, VIPRS_CS_E = 5,
+                       VIPRS_CS_BUFFER_COUNT = 6 };
+#define VIPRS_CS_KEEP_VARIATES 1
+#define VIPRS_CS_PREPARE_ONLY 2
+#define VIPRS_N_CS_SUMS 4
+int viprs_state_cs_variates(viprs_state* state, uint64_t seed, uint64_t draw_index, const int32_t* active_model_idx, int n_active);
+int viprs_state_cs_update(viprs_state* state, int n, const double* params, double psi_max, uint64_t seed, uint64_t draw_index,
+                          int flags, int sync);
+int viprs_state_cs_sums(viprs_state* state, int n, const int32_t* cols, double* out);
+int viprs_state_cs_upload(viprs_state* state, int which, const void* host);
+int viprs_state_cs_download(viprs_state* state, int which, void* host);
+int viprs_plan_last_cs_ms(viprs_plan* plan, double* variates_ms, double* update_ms);
+
 /* ---- LD product: Y = R B over EVERY block of a plan -------------------------------------------------------------------
  * What the reference computes with `ld.dot(B)`: the pseudo-validation metrics against a validation LD panel
  * (viprs/eval/pseudo_metrics.py:122-127: R_val B for all grid models at once) and q + beta = R beta for effects that were

@@ -35,6 +35,9 @@ PANEL_ELASTIC_NET, BAND_ELASTIC_NET = 4, 3          # model constants of the ela
 PANEL_GIBBS, BAND_GIBBS = 5, 4                      # ... of the Gibbs route (viprs_gibbs_route)
 GIBBS_UNIF, GIBBS_NOISE, GIBBS_MEAN_SUM = 0, 1, 2   # viprs_gibbs_buffer
 GIBBS_KEEP_DRAWS = 1
+CS_PSI, CS_DELTA, CS_UB, CS_Z1, CS_Z2, CS_E = range(6)   # viprs_cs_buffer
+CS_KEEP_VARIATES, CS_PREPARE_ONLY = 1, 2
+N_CS_SUMS = 4
 COMM_ID_BYTES = 128
 
 
@@ -144,6 +147,12 @@ _PROTOS = {
     "viprs_state_gibbs_reset_mean": (_i, [_vp]),
     "viprs_gibbs_route": (_i, [_i] * 4 + [ctypes.POINTER(_i)]),
     "viprs_plan_last_gibbs_draws_ms": (_i, [_vp, ctypes.POINTER(_d)]),
+    "viprs_state_cs_variates": (_i, [_vp, _u64, _u64, _vp, _i]),
+    "viprs_state_cs_update": (_i, [_vp, _i, _vp, _d, _u64, _u64, _i, _i]),
+    "viprs_state_cs_sums": (_i, [_vp, _i, _vp, _vp]),
+    "viprs_state_cs_upload": (_i, [_vp, _i, _vp]),
+    "viprs_state_cs_download": (_i, [_vp, _i, _vp]),
+    "viprs_plan_last_cs_ms": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_d)]),
     "viprs_plan_dot": (_i, [_vp, _i, _i, _vp, _vp, _d, _i]),
     "viprs_state_dot": (_i, [_vp, _i, _d, _i, _vp]),
     "viprs_plan_last_dot_ms": (_i, [_vp, ctypes.POINTER(_d)]),

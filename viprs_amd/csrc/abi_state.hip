@@ -298,6 +298,44 @@ __global__ __launch_bounds__(kSumsBlock) void enet_sums_kernel(SumsRow one, cons
         partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kNEnetSums + threadIdx.x] = red[threadIdx.x][0];
 }
 
+// The sums of PRS-CS (viprs_state_cs_sums), fp32 grid states: the same row scheme once more.  The four sums travel with a
+// fifth slot, a maximum over nothing (0), because sums_final_kernel takes the last sum of a row for one.
+constexpr int kNCsSums = VIPRS_N_CS_SUMS + 1;
+__global__ __launch_bounds__(kSumsBlock) void cs_sums_kernel(SumsRow one, const SumsRow* __restrict__ rows,
+                                                             const float* __restrict__ eta, const float* __restrict__ psi,
+                                                             const float* __restrict__ delta, const double* __restrict__ n_snp,
+                                                             double* __restrict__ partials) {
+    SumsRow r;
+    if (rows) r = rows[blockIdx.y];
+    else r = one;
+    if ((int)blockIdx.x >= r.nb) return;
+    __shared__ double red[VIPRS_N_CS_SUMS][kSumsBlock];
+    double acc[VIPRS_N_CS_SUMS];
+#pragma unroll
+    for (int k = 0; k < VIPRS_N_CS_SUMS; ++k) acc[k] = 0.0;
+    for (int64_t i = r.i0 + (int64_t)blockIdx.x * kSumsBlock + threadIdx.x; i < r.i1; i += (int64_t)r.nb * kSumsBlock) {
+        const double e = (double)eta[r.off + i], p = (double)psi[r.off + i];
+        const double t = e * e / p;
+        acc[0] += t;
+        acc[1] += n_snp[i] * t;
+        acc[2] += (double)delta[r.off + i];
+        acc[3] += p;
+    }
+#pragma unroll
+    for (int k = 0; k < VIPRS_N_CS_SUMS; ++k) red[k][threadIdx.x] = acc[k];
+    __syncthreads();
+    for (int s = kSumsBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+#pragma unroll
+            for (int k = 0; k < VIPRS_N_CS_SUMS; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < kNCsSums)
+        partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kNCsSums + threadIdx.x] =
+            threadIdx.x < VIPRS_N_CS_SUMS ? red[threadIdx.x % VIPRS_N_CS_SUMS][0] : 0.0;
+}
+
 // stage 2, every family: workgroup (k, y) is one wave adding sum k over the `nb` partials of row y (`stride` slots per row):
 // lane l adds the partials of workgroups l, l + 64, ... in order, then a fixed xor-shuffle tree combines the 64 lanes -- a
 // deterministic order whatever the timing; the last sum of a row is a maximum
@@ -555,7 +593,7 @@ static int sums_buffers(viprs_state* S, size_t partials, size_t total) {
 }
 
 // the first-stage kernel of a reduction (callers that pass a bool mean the first two)
-enum { kSumsSpikeSlabOrGrid = 0, kSumsMixture = 1, kSumsElasticNet = 2 };
+enum { kSumsSpikeSlabOrGrid = 0, kSumsMixture = 1, kSumsElasticNet = 2, kSumsCs = 3 };
 
 // Enqueues the reduction of `one` (kernel argument) or of the `n` rows in the sums staging (one H2D copy), n_sums sums per
 // row, by the first-stage kernel `family`, then the all-rank reduction and the asynchronous copy into h_sums; sums_collect waits for it.  A rank whose plan
@@ -585,6 +623,10 @@ static int sums_enqueue(viprs_state* S, int family, int n, int n_sums, const Sum
                 *h, rows, (const float*)S->f[VIPRS_FIELD_ETA].p, (const float*)S->f[VIPRS_FIELD_Q].p,
                 (const float*)S->f[VIPRS_FIELD_ETA_DIFF].p, (const float*)S->f[VIPRS_FIELD_STD_BETA].p,
                 (const float*)S->f[VIPRS_FIELD_ENET_PENALTY].p, S->d_partials.p);
+        else if (family == kSumsCs)
+            cs_sums_kernel<<<grid, kSumsBlock, 0, P->stream>>>(
+                *h, rows, (const float*)S->f[VIPRS_FIELD_ETA].p, S->d_cs.p + (size_t)VIPRS_CS_PSI * P->m * S->width,
+                S->d_cs.p + (size_t)VIPRS_CS_DELTA * P->m * S->width, S->d_n.p, S->d_partials.p);
         else if (mixture && S->float_dtype == VIPRS_F32)
             sums_mixture_kernel<float><<<grid, kSumsBlock, 0, P->stream>>>(S->width, VIPRS_SUMS_ARGS(float), S->d_log_var_tau0.p,
                                                                            S->d_partials.p);
@@ -884,6 +926,43 @@ int viprs_state_enet_sums(viprs_state* S, int n, const int32_t* cols, double* ou
         out[i * kNEnetSums] = g[kNEnetSums - 1];
         for (int k = 1; k < kNEnetSums; ++k) out[i * kNEnetSums + k] = g[k - 1];
     }
+    return VIPRS_OK;
+}
+
+int viprs_state_cs_sums(viprs_state* S, int n, const int32_t* cols, double* out) {
+    int rc = cs_state_check(S, "sums");
+    if (rc != VIPRS_OK) return rc;
+    if (!out) return fail(VIPRS_EINVAL, "PRS-CS sums: out is null");
+    if (n < 0 || n > S->width) return fail(VIPRS_EINVAL, "PRS-CS sums: bad column count");
+    if (!cols && n != S->width) return fail(VIPRS_EINVAL, "PRS-CS sums: cols == NULL lists every column: n must be the state's width");
+    std::vector<char> seen((size_t)S->width, 0);
+    for (int i = 0; cols && i < n; ++i) {
+        if (cols[i] < 0 || cols[i] >= S->width) return fail(VIPRS_EINVAL, "PRS-CS sums: column out of range");
+        if (seen[(size_t)cols[i]]) return fail(VIPRS_EINVAL, "PRS-CS sums: a column is listed twice");
+        seen[(size_t)cols[i]] = 1;
+    }
+    viprs_plan* P = S->plan;
+    if (P->m > 0 && !S->d_n.p) return fail(VIPRS_EINVAL, "PRS-CS sums: viprs_state_set_n_per_snp has not been called");
+    for (int k = 0; k < n * VIPRS_N_CS_SUMS; ++k) out[k] = 0.0;
+    if (n == 0 || P->m == 0) return VIPRS_OK;
+    HIP_TRY(hipSetDevice(P->device));
+    rc = cs_ensure_buffers(S);
+    if (rc != VIPRS_OK) return rc;
+    rc = row_buffers(S, n);
+    if (rc != VIPRS_OK) return rc;
+    // (the sums staging is free: the previous reduction that read it has been collected)
+    SumsRow* h = sums_staging(S);
+    for (int i = 0; i < n; ++i) {
+        h[i] = sums_row(S, 0, P->m, cols ? cols[i] : i, 0.0, false, nullptr);
+        h[i].nb = grid_sums_blocks(P->m);                     // THE ORDER of a grid state's rows
+    }
+    rc = sums_enqueue(S, kSumsCs, n, kNCsSums, nullptr);
+    if (rc != VIPRS_OK) return rc;
+    std::vector<double> got((size_t)n * kNCsSums);
+    rc = sums_collect(S, got.data(), "viprs_state_cs_sums");
+    if (rc != VIPRS_OK) return rc;
+    for (int i = 0; i < n; ++i)                               // (the fifth slot is the empty maximum of the final pass)
+        for (int k = 0; k < VIPRS_N_CS_SUMS; ++k) out[i * VIPRS_N_CS_SUMS + k] = got[(size_t)i * kNCsSums + k];
     return VIPRS_OK;
 }
 

@@ -294,6 +294,7 @@ struct viprs_plan {
     viprs::DevBuf<viprs::RidgeBlock> d_solver_blocks;   // start and size of every LD block, SNP order (ensure_solver_blocks)
     viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
     viprs::EventBracket time_gibbs_draws;          // the draws kernel of the Gibbs sweeps (abi_gibbs.hip)
+    viprs::EventBracket time_cs_variates, time_cs_update;   // the two PRS-CS kernels (abi_cs.hip)
     viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
 
     ~viprs_plan();
@@ -338,6 +339,10 @@ struct viprs_state {
     // (m, G) float64 sum of the Rao-Blackwellised means
     viprs::DevBuf<float> d_gibbs_draws;
     viprs::DevBuf<double> d_gibbs_mean;
+    // PRS-CS (abi_cs.hip), allocated by the first cs call: the VIPRS_CS_BUFFER_COUNT (m, G) float32 buffers of
+    // viprs_cs_buffer in ONE allocation, in the order of the enum; the (column, sigma2, phi) rows of the call in flight
+    viprs::DevBuf<float> d_cs;
+    viprs::DevBuf<double> d_cs_rows;
     ~viprs_state() {
         if (h_sums) (void)hipHostFree(h_sums);
         if (h_rows) (void)hipHostFree(h_rows);
@@ -424,6 +429,10 @@ template <typename U> int launch_band_gibbs(viprs_plan* P, EStepArgs<float> A);
 int gibbs_ensure_draws(viprs_state* S);
 int gibbs_enqueue_draws(viprs_state* S, uint64_t seed, uint64_t draw_index, const int32_t* d_active, int n_active);
 const float* gibbs_draws_slot(const viprs_state* S);
+// abi_cs.hip: what every PRS-CS entry point refuses (`what` names the call in the message), and the state's cs buffers
+// (psi = 1, the rest zero), created by the first call that needs them
+int cs_state_check(const viprs_state* S, const char* what);
+int cs_ensure_buffers(viprs_state* S);
 // batched grid E-step on the matrix cores
 template <typename U> int launch_grid_mfma(viprs_plan* P, EStepArgs<float> A);
 // LD product Y = dq_scale (R - diag) B (+ B) over every block of the plan (ld_dot.h); device pointers, (m, n_cols) column-major

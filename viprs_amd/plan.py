@@ -381,6 +381,13 @@ class LDPlan:
         L.check(L.lib.viprs_plan_last_gibbs_draws_ms(self.handle, ctypes.byref(ms)))
         return ms.value
 
+    def last_cs_ms(self):
+        """Event times (ms) of the last PRS-CS variates kernel and of the last update kernel on this plan
+        (`viprs_plan_last_cs_ms`; 0 for one that has not run)."""
+        v, u = ctypes.c_double(), ctypes.c_double()
+        L.check(L.lib.viprs_plan_last_cs_ms(self.handle, ctypes.byref(v), ctypes.byref(u)))
+        return v.value, u.value
+
     def last_clump_ms(self):
         """HIP-event time (ms) of the kernels of the last `clump` on this plan."""
         ms = ctypes.c_double(0.0)
@@ -925,6 +932,45 @@ class DeviceState:
         if a.dtype != dt or a.shape != (self.plan.m, self.width) or not a.flags.f_contiguous:
             raise ValueError(f"{which}: a Fortran-contiguous {np.dtype(dt).name} array of shape {(self.plan.m, self.width)}")
         L.check(L.lib.viprs_state_gibbs_upload(self._h, code, _ptr(a)))
+
+    # -- PRS-CS: the local scales psi between two Gibbs sweeps --------------------------------------------
+    _CS = {"psi": L.CS_PSI, "delta": L.CS_DELTA, "ub": L.CS_UB, "z1": L.CS_Z1, "z2": L.CS_Z2, "e": L.CS_E}
+
+    def cs_variates(self, seed, draw_index, active_model_idx=None):
+        """The variates ``ub, z1, z2, e`` of the listed columns (default: every column) of a float32 grid state
+        (`viprs_state_cs_variates`, include/viprs_hip.h; `viprs_amd.stats.cs.cs_variates_host`)."""
+        a, n = self._active(active_model_idx)
+        L.check(L.lib.viprs_state_cs_variates(self._h, int(seed), int(draw_index), None if a is None else _ptr(a), n))
+
+    def cs_update(self, params, psi_max=1.0, seed=0, draw_index=0, keep_variates=False, prepare_only=False, sync=True):
+        """New local scales ``psi`` (and ``delta``) for the chains of `params` -- rows ``(column, sigma2, phi)`` -- and the
+        inputs ``mu_mult``, ``half_var_tau``, ``u_logs`` of the next `gibbs_sweep` (`viprs_state_cs_update`;
+        `viprs_amd.stats.cs.cs_update_host`).  `prepare_only`: the inputs from the stored psi, nothing drawn."""
+        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3)
+        flags = (L.CS_KEEP_VARIATES if keep_variates else 0) | (L.CS_PREPARE_ONLY if prepare_only else 0)
+        L.check(L.lib.viprs_state_cs_update(self._h, int(p.shape[0]), _ptr(p), float(psi_max), int(seed), int(draw_index), flags,
+                                            int(bool(sync))))
+
+    def cs_sums(self, cols=None):
+        """``(n, 4)`` float64, one row per listed column (default: every column): sum eta^2 / psi, sum n_j eta^2 / psi,
+        sum delta, sum psi (`viprs_state_cs_sums`)."""
+        c = None if cols is None else np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32)
+        n = self.width if c is None else int(c.shape[0])
+        out = np.zeros((n, L.N_CS_SUMS), dtype=np.float64)
+        L.check(L.lib.viprs_state_cs_sums(self._h, n, None if c is None else _ptr(c), _ptr(out)))
+        return out
+
+    def cs_download(self, which):
+        """``"psi"``, ``"delta"``, ``"ub"``, ``"z1"``, ``"z2"`` or ``"e"``: float32 ``(m, G)`` column-major."""
+        out = np.zeros((self.plan.m, self.width), dtype=np.float32, order="F")
+        L.check(L.lib.viprs_state_cs_download(self._h, self._CS[which], _ptr(out)))
+        return out
+
+    def cs_upload(self, which, array):
+        a = np.asarray(array)
+        if a.dtype != np.float32 or a.shape != (self.plan.m, self.width) or not a.flags.f_contiguous:
+            raise ValueError(f"{which}: a Fortran-contiguous float32 array of shape {(self.plan.m, self.width)}")
+        L.check(L.lib.viprs_state_cs_upload(self._h, self._CS[which], _ptr(a)))
 
     def dot(self, name="eta", dq_scale=1.0, include_diagonal=True):
         """``R @ eta`` with the resident posterior mean as `B` (`viprs_state_dot`): only the ``m x n_cols`` results cross to
