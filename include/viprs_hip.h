@@ -818,6 +818,68 @@ int viprs_plan_extremal_eigenvalues(viprs_plan* plan, int float_dtype, double dq
 int viprs_plan_last_spectrum_ms(viprs_plan* plan, double* total_ms, int* iterations, double* host_ms /* nullable */);
 int viprs_tridiagonal_extremes(int k, const double* alpha, const double* beta, double* out);
 
+/* ---- SuSiE fine-mapping: L single effects per LD block, lock-step single-effect updates -----------------------------------
+ * SuSiE-RSS (Wang et al. 2020; Zou et al. 2022) on z-scores, independently for every LD block of the plan (blocks as
+ * viprs_plan_get_blocks lists them, SNP order): z ~ N(R b, R) with the residual variance fixed at 1 (`susie_rss` with
+ * estimate_residual_variance = FALSE), b = sum_{l < L} b_l, every b_l a single effect: exactly one SNP j is non-zero, chosen
+ * with prior pi_j, its value N(0, V_l).  R = unit diagonal + dq_scale * stored off-diagonal entries: exactly the matrix of
+ * viprs_plan_dot(..., include_diagonal = 1).  The reference tree has no fine-mapping model, so nothing here is a parity
+ * claim: the definition below is the contract.
+ *   z            (m,) doubles, finite
+ *   log_prior    (m,) doubles, log pi_j; -inf excludes a SNP (not every SNP of a block); NULL: -log(block size), the host
+ *                libm's log of the size as a double
+ *   prior var.   V start: (n_blocks, L) row-major doubles, or NULL and `prior_variance0` for every effect; finite, >= 0
+ *   state        alpha, mu, Rb: (m, L) column-major in the state precision T (`float_dtype`), all zero at the start;
+ *                bbar, Y: (m,) in T; V, post_var: (n_blocks, L) doubles
+ *   a step       effect l of iteration it (it = 1, 2, ...; l = 0 .. L - 1), for every SNP j of a block that is still running.
+ *                Every operation below is one IEEE double operation on the values named, no contraction; (T)x is one rounding
+ *                to the state precision, (double)x the exact conversion of a stored T value:
+ *                  0. unless this is the first step of the call: Rb[j, (l - 1) mod L] = Y[j], the product launched by the
+ *                     step before
+ *                  1. a_j = ((0 + (double)Rb[j, l'_1]) + (double)Rb[j, l'_2]) + ... over l' != l in ascending l';
+ *                     r_j = z_j - a_j.  Recomputed at every step: no running total
+ *                  2. s = V_l / (1 + V_l);  w_j = (0.5 * (r_j * r_j)) * s + log pi_j;  mu[j, l] = (T)(s * r_j).
+ *                     (-0.5 log(1 + V_l) of the log Bayes factor is constant over the block and cancels below)
+ *                  3. wmax = max_j w_j;  e_j = exp(w_j - wmax) with the host libm's exp (glibc 2.35, bit for bit);
+ *                     m_j = (double)mu[j, l];  S = sum_j e_j;  Q = sum_j e_j * (s + m_j * m_j)
+ *                  4. alpha[j, l] = (T)(e_j / S);  bbar_j = (T)((double)alpha[j, l] * m_j);  post_var[l] = s
+ *                  5. estimate_prior_variance: V_l <- Q / S (the EM update; it takes effect at the effect's next visit).
+ *                     V_l = 0 needs no special case: alpha = pi, mu = 0
+ *                  6. delta_it = max(delta_it, max_j |(double)alpha[j, l] - (double)alpha_old[j, l]|), alpha_old = what the
+ *                     buffer held (0 before the first iteration); delta_it starts from 0 at l = 0
+ *                  7. Y = R bbar is launched (viprs_plan_dot's kernels, one column, in T)
+ *   order        S and Q are summed in the order of the ridge solve's dot products: 16-byte chunks of T (4 float32, 2
+ *                float64 elements) dealt to 256 threads in turn, one double accumulator per thread adding in ascending
+ *                order, the xor butterfly over the 64 lanes, the wavefronts in order.  The maxima are order-free.  No
+ *                floating-point atomics
+ *   stopping     after effect L - 1 of iteration it a block is converged (status 0) if delta_it < tol, otherwise stopped at
+ *                max_iter (status 1) if it >= max_iter.  A block whose status is final is frozen: later launches leave every
+ *                one of its outputs unchanged.  The number of running blocks is read back every `check_every` iterations:
+ *                the only synchronisation inside the loop
+ *   outputs      alpha, mu ((m, L) column-major, T), prior_variance_out (V after its last update), post_var_out, and per
+ *                block iterations done, the last delta_it and the status (each of the last five may be NULL)
+ * A block's bits depend on its own entries, its z, its log pi, L, the V start, tol, max_iter and its size: not on its place
+ * in the plan, on the other blocks, on `check_every` or on timing; two calls give identical bits.
+ * NOT BUILT: susieR's `optim` estimator of V and its null check, residual-variance estimation, the n-adjusted z of
+ * susie_rss, lambda regularisation, several ranks, a fast-math variant, skipping the LD rows of frozen blocks (the product
+ * streams the whole plan).  viprs_plan_set_active_blocks does NOT filter the call.  The workspace lives on the plan and is
+ * reused.  Windowed plans and the dense blocks of the upper form are read as the product reads them.
+ * Bad dtype code, L outside 1..32, tol <= 0, max_iter < 1, check_every < 1, dq_scale not finite or <= 0, a negative or
+ * non-finite prior variance, a non-finite z, a log_prior that is NaN, +inf or -inf over a whole block, a null plan / z /
+ * alpha / mu: VIPRS_EINVAL before any launch, outputs untouched.  An empty plan returns VIPRS_OK.
+ *   viprs_plan_last_susie_ms  HIP-event time from the first to the last kernel of the last call on this plan (the read-backs
+ *                             of the loop included), the step kernels it launched, and (nullable) the time of ONE step
+ *                             kernel: effect L - 1 of iteration 1, when every block is still running */
+int viprs_plan_susie(viprs_plan* plan, int float_dtype, int L, const double* z_host,
+                     const double* log_prior_host /* nullable: -log(block size) */,
+                     const double* prior_variance_host /* (n_blocks, L), or NULL with prior_variance0 */,
+                     double prior_variance0, int estimate_prior_variance, double dq_scale,
+                     double tol, int max_iter, int check_every,
+                     void* alpha_host, void* mu_host,              /* (m, L) column-major, T */
+                     double* prior_variance_out, double* post_var_out,   /* (n_blocks, L) */
+                     int32_t* block_iters, double* block_delta, int32_t* block_status /* each nullable */);
+int viprs_plan_last_susie_ms(viprs_plan* plan, double* total_ms, int* steps, double* step_kernel_ms);
+
 /* ---- genotype scoring: PLINK .bed rows on the device, per-SNP code counts, polygenic scores ------------------------------
  * What a fitted model is for: score(i, c) = sum_j B[j, c] * dose_j(genotype of sample i at SNP j).  The reference hands this to
  * plink2 through magenpy (BayesPRSModel.predict -> GWADataLoader.predict); neither is part of the reference tree, so nothing

@@ -165,6 +165,8 @@ _PROTOS = {
     "viprs_plan_extremal_eigenvalues": (_i, [_vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "viprs_plan_last_spectrum_ms": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_i), ctypes.POINTER(_d)]),
     "viprs_tridiagonal_extremes": (_i, [_i, _vp, _vp, _vp]),
+    "viprs_plan_susie": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d, _i, _d, _d, _i, _i] + [_vp] * 7),
+    "viprs_plan_last_susie_ms": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_i), ctypes.POINTER(_d)]),
     "viprs_genotypes_create": (_i, [ctypes.POINTER(_vp), _i64, _i64, _i]),
     "viprs_genotypes_upload_rows": (_i, [_vp, _i64, _i64, _vp]),
     "viprs_genotypes_destroy": (_i, [_vp]),

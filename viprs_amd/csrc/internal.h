@@ -203,6 +203,18 @@ struct SpectrumWork {
     double host_ms = 0.0;                          // host time of its checks (downloads + tridiagonal eigenproblems)
 };
 
+// SuSiE fine-mapping (abi_susie.hip, susie.h): the workspace of a plan, allocated by its first call and reused
+struct SusieWork {
+    DevBuf<char> d_rec;                            // SusieRec per LD block, SNP order
+    DevBuf<int32_t> d_live;                        // blocks still running
+    DevBuf<char> d_alpha, d_mu, d_rb;              // (m, L) each, state precision
+    DevBuf<char> d_bbar, d_y;                      // (m,): the product's input and result
+    DevBuf<double> d_w, d_z, d_log_pi;             // (m,)
+    DevBuf<double> d_v, d_v0, d_post_var;          // (n_blocks, L)
+    EventBracket time, time_step;                  // the whole call; the step kernel of effect L - 1 of iteration 1
+    int steps = 0;                                 // step kernels the last call launched
+};
+
 }  // namespace viprs
 
 struct viprs_state;
@@ -296,6 +308,7 @@ struct viprs_plan {
     viprs::EventBracket time_gibbs_draws;          // the draws kernel of the Gibbs sweeps (abi_gibbs.hip)
     viprs::EventBracket time_cs_variates, time_cs_update;   // the two PRS-CS kernels (abi_cs.hip)
     viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
+    viprs::SusieWork susie;                        // viprs_plan_susie
 
     ~viprs_plan();
 };

@@ -5,13 +5,14 @@ from .ClumpThreshold import ClumpThreshold
 from .Lassosum import Lassosum
 from .LDpred2 import LDpred2
 from .PRSCS import PRSCS
+from .SuSiE import SuSiE
 from .VIPRSPerChromosome import VIPRSPerChromosome
 from .VIPRSMixPerChromosome import VIPRSMixPerChromosome
 from .gridsearch import (HyperparameterGrid, VIPRSGrid, VIPRSGridPathwisePerChromosome, VIPRSGridPerChromosome,
                          bayesian_model_average, bayesian_model_average_per_chromosome, select_best_model,
                          select_best_model_per_chromosome)
 
-__all__ = ["VIPRS", "VIPRSMix", "LDPredInf", "ClumpThreshold", "Lassosum", "LDpred2", "PRSCS", "VIPRSPerChromosome", "VIPRSMixPerChromosome", "VIPRSGrid", "VIPRSGridPerChromosome",
+__all__ = ["VIPRS", "VIPRSMix", "LDPredInf", "ClumpThreshold", "Lassosum", "LDpred2", "PRSCS", "SuSiE", "VIPRSPerChromosome", "VIPRSMixPerChromosome", "VIPRSGrid", "VIPRSGridPerChromosome",
            "VIPRSGridPathwisePerChromosome",
            "HyperparameterGrid", "select_best_model", "bayesian_model_average", "select_best_model_per_chromosome",
            "bayesian_model_average_per_chromosome"]

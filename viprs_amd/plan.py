@@ -14,6 +14,8 @@ import numpy as np
 
 from . import _lib as L
 
+_LIB = L                       # (for the methods that take an argument named L)
+
 _FLOAT_CODE = {np.dtype(np.float32): L.F32, np.dtype(np.float64): L.F64}
 _LD_CODE = {np.dtype(np.int8): L.LD_I8, np.dtype(np.int16): L.LD_I16, np.dtype(np.int32): L.LD_I32,
             np.dtype(np.int64): L.LD_I64, np.dtype(np.float32): L.LD_F32, np.dtype(np.float64): L.LD_F64}
@@ -73,6 +75,54 @@ class RidgeInfo:
     def __repr__(self):
         return (f"RidgeInfo(blocks={self.status.shape[0]}, converged={self.converged}, "
                 f"max_iterations={int(self.iterations.max(initial=0))}, ms={self.ms:.3f})")
+
+
+class SusieInfo:
+    """What a SuSiE fit reports (`LDPlan.susie`, `viprs_amd.stats.susie.susie_host`): `alpha`, `mu` ``(m, L)``; per LD
+    block (SNP order) `prior_variance`, `post_var` ``(n_blocks, L)``, `iterations`, `delta` (the last iteration's
+    max |alpha - alpha_old|) and `status` (0 converged, 1 stopped at max_iter); `block_start` (``n_blocks + 1`` SNP offsets);
+    `converged`: no block stopped at max_iter; `ms`: device time of the call."""
+    CONVERGED, MAXITER = 0, 1
+
+    def __init__(self, alpha, mu, prior_variance, post_var, iterations, delta, status, block_start, ms=0.0):
+        self.alpha = np.asarray(alpha)
+        self.mu = np.asarray(mu)
+        self.prior_variance = np.asarray(prior_variance, dtype=np.float64)
+        self.post_var = np.asarray(post_var, dtype=np.float64)
+        self.iterations = np.asarray(iterations, dtype=np.int32)
+        self.delta = np.asarray(delta, dtype=np.float64)
+        self.status = np.asarray(status, dtype=np.int32)
+        self.block_start = np.asarray(block_start, dtype=np.int64)
+        self.ms = float(ms)
+
+    @property
+    def converged(self):
+        return bool(np.all(self.status != self.MAXITER))
+
+    def __repr__(self):
+        return (f"SusieInfo(blocks={self.status.shape[0]}, L={self.alpha.shape[1] if self.alpha.ndim == 2 else 0}, "
+                f"converged={self.converged}, max_iterations={int(self.iterations.max(initial=0))}, ms={self.ms:.3f})")
+
+
+def susie_inputs(m, n_blocks, z, L, prior_variance, log_prior):
+    """The arrays of a SuSiE call as the C ABI takes them: ``(z, prior_variance array or None, prior_variance0, log_prior or
+    None)``.  Shapes are checked here; the values are the library's to refuse."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    if z.shape != (m,):
+        raise ValueError(f"z: expected shape ({m},), got {z.shape}")
+    v = np.asarray(prior_variance, dtype=np.float64)
+    if v.ndim == 0:
+        v, v0 = None, float(v)
+    else:
+        if v.shape != (n_blocks, int(L)):
+            raise ValueError(f"prior_variance: expected a scalar or shape ({n_blocks}, {int(L)}), got {v.shape}")
+        v, v0 = np.ascontiguousarray(v), 0.0
+    lp = None
+    if log_prior is not None:
+        lp = np.ascontiguousarray(log_prior, dtype=np.float64)
+        if lp.shape != (m,):
+            raise ValueError(f"log_prior: expected shape ({m},), got {lp.shape}")
+    return z, v, v0, lp
 
 
 class SpectrumInfo:
@@ -440,6 +490,43 @@ class LDPlan:
         ms, n = ctypes.c_double(0.0), ctypes.c_int(0)
         L.check(L.lib.viprs_plan_last_solve_ms(self.handle, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+    # -- SuSiE fine-mapping ------------------------------------------------------------------------
+    def susie(self, z, L=10, prior_variance=50.0, estimate_prior_variance=True, log_prior=None, dq_scale=1.0, tol=1e-4,
+              max_iter=100, check_every=4, float_precision="float32"):
+        """SuSiE-RSS on z-scores, one fit of `L` single effects per LD block, all blocks in lock step (`viprs_plan_susie`):
+        ``z ~ N(R b, R)``, `R` as in `dot` with the diagonal.  `z`: ``(m,)``; `prior_variance`: a scalar or
+        ``(n_blocks, L)``, the start of the EM update with `estimate_prior_variance`; `log_prior`: ``(m,)`` log pi_j (-inf
+        excludes a SNP), None: uniform over each block.  Returns a `SusieInfo`; `alpha` and `mu` are ``(m, L)`` in
+        `float_precision`.  `set_active_blocks` does not filter the call."""
+        dt = np.dtype(float_precision)
+        if dt not in _FLOAT_CODE:
+            raise ValueError(f"float_precision: expected float32 or float64, got {float_precision}")
+        starts = self.blocks()[0]
+        n_blocks = len(starts) - 1
+        z, v, v0, lp = susie_inputs(self.m, n_blocks, z, L, prior_variance, log_prior)
+        L_ = int(L)
+        alpha = np.zeros((self.m, max(L_, 0)), dtype=dt, order="F")
+        mu = np.zeros((self.m, max(L_, 0)), dtype=dt, order="F")
+        v_out = np.zeros((n_blocks, max(L_, 0)))
+        post_var = np.zeros((n_blocks, max(L_, 0)))
+        iters = np.zeros(n_blocks, dtype=np.int32)
+        delta = np.zeros(n_blocks)
+        status = np.zeros(n_blocks, dtype=np.int32)
+        _LIB.check(_LIB.lib.viprs_plan_susie(self.handle, _FLOAT_CODE[dt], L_, _ptr(z), _ptr(lp), _ptr(v), float(v0),
+                                       int(bool(estimate_prior_variance)), float(dq_scale), float(tol), int(max_iter),
+                                       int(check_every), _ptr(alpha), _ptr(mu), _ptr(v_out), _ptr(post_var), _ptr(iters),
+                                       _ptr(delta), _ptr(status)))
+        ms = self.last_susie_ms()[0] if self.m else 0.0
+        return SusieInfo(alpha, mu, v_out, post_var, iters, delta, status, starts, ms)
+
+    def last_susie_ms(self):
+        """``(ms, steps, step_kernel_ms)`` of the last `susie` on this plan: HIP-event time from its first to its last
+        kernel, the step kernels it launched, and the time of one step kernel (effect L - 1 of iteration 1: every block is
+        still running)."""
+        ms, n, step = ctypes.c_double(0.0), ctypes.c_int(0), ctypes.c_double(0.0)
+        L.check(L.lib.viprs_plan_last_susie_ms(self.handle, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(step)))
+        return ms.value, n.value, step.value
 
     # -- extremal eigenvalues ---------------------------------------------------------------------
     def extremal_eigenvalues(self, dq_scale=1.0, rtol=None, maxiter=None, float_precision="float32"):

@@ -6,3 +6,4 @@ from .clump import clump_host, clump_order  # noqa: F401  (`stats.clump` stays t
 from .enet import enet_objective, enet_sums_host, enet_sweep_host, lambda_path  # noqa: F401
 from .gibbs import gibbs_draws_host, gibbs_sweep_host, philox4x32_10  # noqa: F401  (`stats.gibbs.gibbs_route` stays in the module)
 from .cs import cs_sums_host, cs_update_host, cs_variates_host, gig_half_from_variates  # noqa: F401
+from .susie import credible_sets, pips, susie_elbo, susie_host  # noqa: F401
