@@ -129,11 +129,17 @@ __device__ __forceinline__ float sigmoid_exact(float x, const ExpTab& tab, int s
 // Error: v_exp_f32's 1 ulp + 2^-23 -- a few 1e-7 relative for every argument (an uncompensated product is off by
 // |x| * 1e-7, 1e-5 at x = -100), against 1e-5 allowed.  Arguments below -126 / log2(e) give denormal or zero
 // results like expf's (v_exp_f32 flushes at 2^-126: below the resolution of anything the E-step adds them to).
+// The correction is formed from a copy of t clamped at -256 (and that copy's own product): for t >= -256 the bits are
+// those of t itself; below, e0 = 0 and any finite factor leaves 0.  Without the clamp t = -inf, and every t below
+// -FLT_MAX / log2(e) whose product overflows, gave perr = inf - inf and the sigmoid of +-inf came out NaN instead of
+// 1 / 0 (tests/test_gpu_math_range.py).  The clamp and the second product are off the chain, like the rest of perr;
+// a NaN argument still comes out NaN through p.
 __device__ __forceinline__ float expf_fast_nonpos(float t) {
     const float L_hi = 0x1.715476p+0f;         // log2(e) rounded to float
     const float L_lo = 0x1.4ae0cp-26f;         // log2(e) - L_hi
     const float p = t * L_hi;
-    const float perr = __builtin_fmaf(t, L_lo, __builtin_fmaf(t, L_hi, -p));
+    const float tc = __builtin_fmaxf(t, -256.0f);
+    const float perr = __builtin_fmaf(tc, L_lo, __builtin_fmaf(tc, L_hi, -(tc * L_hi)));
     const float k = perr * 0x1.62e43p-1f;      // ln2 * perr (off the critical path)
     const float e0 = __builtin_amdgcn_exp2f(p);
     return __builtin_fmaf(e0, k, e0);
