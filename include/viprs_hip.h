@@ -412,9 +412,11 @@ enum viprs_sweep_family {
     VIPRS_FAMILY_GENERIC = 1,        /* row-by-row kernels (called for an empty list too: they return at once) */
     VIPRS_FAMILY_TILE_F64 = 2,       /* float64 states: the panel-walking kernels (likewise) */
     VIPRS_FAMILY_PANEL = 3,          /* the panel sweep; model 0 spike-and-slab, 1 grid column, 2 mixture K <= 8, 3 mixture K <= 31
-                                        (4: the elastic net, viprs_enet_route only; 5: the Gibbs draw, viprs_gibbs_route only) */
+                                        (4: the elastic net, viprs_enet_route only; 5: the Gibbs draw, viprs_gibbs_route only; 6: SBayesR,
+                                        viprs_bayesr_route only) */
     VIPRS_FAMILY_BAND = 4,           /* band kernel of the windowed blocks; model 0 spike-and-slab, 1 grid column, 2 mixture
-                                        (3: the elastic net, viprs_enet_route only; 4: the Gibbs draw, viprs_gibbs_route only) */
+                                        (3: the elastic net, viprs_enet_route only; 4: the Gibbs draw, viprs_gibbs_route only; 5: SBayesR,
+                                        viprs_bayesr_route only) */
     VIPRS_FAMILY_GRID_BATCHED = 5    /* batched grid kernel on the matrix cores: one launch per 32 active columns, a 1-model
                                         prologue launch in front of every launch after the first */
 };
@@ -621,6 +623,84 @@ int viprs_state_cs_sums(viprs_state* state, int n, const int32_t* cols, double* 
 int viprs_state_cs_upload(viprs_state* state, int which, const void* host);
 int viprs_state_cs_download(viprs_state* state, int which, void* host);
 int viprs_plan_last_cs_ms(viprs_plan* plan, double* variates_ms, double* update_ms);
+
+/* ---- SBayesR: a mixture Gibbs draw where the mixture E-step takes an expectation ---------------------------------------------
+ * SBayesR (Lloyd-Jones et al. 2019; GCTB --sbayes R) samples every effect from its conditional posterior under a finite mixture
+ * of normals with a point mass at zero: component k = 1..K has prior variance gamma_k sigma2_beta and weight pi_k, component 0
+ * is the null with weight pi_0; sigma2_e is the residual variance.  With r_j = std_beta_j - q_j and
+ * C_jk = n_j + sigma2_e / (gamma_k sigma2_beta) the conditional of SNP j picks component k with log-weight
+ * log pi_k - 0.5 log(1 + n_j gamma_k sigma2_beta / sigma2_e) + n_j^2 r_j^2 / (2 C_jk sigma2_e) (the null: log pi_0) and then
+ * draws from N(n_j r_j / C_jk, sigma2_e / C_jk): the mixture E-step of viprs_state_e_step under lambda = 0,
+ * tau_beta[k] = 1 / (gamma_k sigma2_beta), sigma_epsilon = sigma2_e, logit_pi[k] = log pi_k and log_null_pi = log pi_0 -- under
+ * these viprs_state_prep_mixture writes mu_mult = n_j / C_jk, sqrt_half_var_tau = sqrt(C_jk / (2 sigma2_e)) and u_logs = the first
+ * two terms of the log-weight -- with a draw stored in eta where the E-step stores sum_k gamma_k mu_k.  The reference has no such
+ * model; the definition is this library's own, stated in full.  All calls: fp32 states of kind VIPRS_MODEL_MIXTURE, K <= 4,
+ * `n_j` from viprs_state_set_n_per_snp.
+ * BUFFERS.  U, z (float32) and k* (int32), each (m,), in ONE allocation of the state, made by the first SBayesR call (zeros) and
+ * freed with the state; mean_sum and pip_sum, (m,) float64, created on first use.  Other states do not grow.
+ * THE DRAWS.  viprs_state_bayesr_draws: for every SNP j one Philox4x32-10 block with the constants and the key of
+ * viprs_state_gibbs_draws and
+ *   counter = (j, 2^30, low 32 bits of draw_index, high 32 bits of draw_index)
+ * (the tag keeps the stream disjoint from the Gibbs draws, whose second word is a column < 2^30, and from the PRS-CS variates,
+ * whose second word has bit 31 set), and from its output words x0, x1, x2, every operation separately rounded in float32:
+ *   U = (2 (x0 >> 9) + 1) * 2^-24;  u1, u2 likewise from x1, x2
+ *   z = sqrtf(-2 logf(u1)) * cospif(2 u2)
+ * U is bit-exact against a host implementation; z carries the device library's logf / cospif (tests/test_gpu_bayesr.py states
+ * the bound).
+ * THE UPDATE.  Per SNP j in index order, from the current q_j, every operation separately rounded in float32, fused
+ * multiply-add only where written, glibc's expf, as e_step_mixture (e_step.hpp:496-537):
+ *   r = fl(std_beta_j - q_j)
+ *   mu_k = fl(mu_mult_jk * r);  t_k = fl(sqrt_half_var_tau_jk * mu_k);  u_k = fma(t_k, t_k, u_logs_jk)              k = 1..K
+ *   mx = max(log_null_pi_j, u_1, .., u_K)
+ *   e_k = expf(u_k - mx);  ssum = ((0 + e_1) + .. + e_K) + expf(log_null_pi_j - mx)            (the null term last)
+ *   gamma_k = fl(e_k / ssum)
+ *   sd_k = fl(0x1.6a09e6p-1f / sqrt_half_var_tau_jk);  n_k = fl(z_j * sd_k)      (0x1.6a09e6p-1f = float32(1 / sqrt 2))
+ *   c_1 = gamma_1;  c_k = fl(c_{k-1} + gamma_k)
+ *   k* = the smallest k in 1..K with U_j < c_k (strict), 0 if there is none
+ *   b = k* ? fl(mu_{k*} + n_{k*}) : +0
+ *   d = fl(b - eta_old_j)
+ *   var_mu[j, k] = mu_k;  var_gamma[j, k] = gamma_k;  eta_diff[j] = d;  eta[j] = b;  kstar[j] = k*
+ * then the E-step's own update of q over the row's window, q[i] = fma(R[j,i], dq_scale * d, q[i]) (symmetric form: followed by
+ * q[j] -= d), and after the block the second pass of the upper form, as for viprs_state_enet_sweep.  There is no skip branch.
+ *   viprs_state_bayesr_sweep  the draws (unless VIPRS_BAYESR_KEEP_DRAWS is set in `flags`: then the sweep uses whatever U and z
+ *                             hold), then one sweep over every LD block the plan's sweeps visit; asynchronous on the plan's
+ *                             stream unless `sync` != 0.  The exact arithmetic whatever the plan's math_mode.
+ * KERNELS.  The panel sweep serves the dense blocks (model 6), one lane per SNP, for fp32, int8 and int16 LD in both forms; the
+ * band kernel serves the windowed ones (model 5) for the same LD types in the symmetric form only.  Sweep timing goes through
+ * the plan's timing record (the draws kernel is outside it); viprs_plan_last_bayesr_draws_ms is the event time of the last draws
+ * kernel.
+ *   viprs_bayesr_route        the route of such a sweep (pure host code; usable without a GPU): prologue and events as the
+ *                             mixture row of viprs_sweep_route, whose arguments and answers are unchanged
+ * THE SUMS.  viprs_state_bayesr_sums, `out`: 2 K + 4 doubles,
+ *   [0 .. K] the number of SNPs with k* = 0 .. K   [K + k] sum eta_j^2 over k*_j = k, k = 1 .. K
+ *   [2K + 1] sum q eta   [2K + 2] sum eta^2   [2K + 3] sum std_beta eta
+ * (viprs_state_enet_sums refuses a mixture state, so its three sums travel here), every term formed in double from the float32
+ * values (no fma), summed in THE ORDER of viprs_state_enet_sums for the row of a spike-and-slab state (cap 1024 workgroups; no
+ * maximum among them).  Synchronous.
+ *   viprs_state_bayesr_accumulate   mean_sum[j] += ((0 + g_1 m_1) + .. + g_K m_K) and pip_sum[j] += ((0 + g_1) + .. + g_K), with
+ *                             g_k = (double)var_gamma[j, k], m_k = (double)var_mu[j, k]: the Rao-Blackwellised posterior mean
+ *                             of the draw and its probability 1 - gamma_0 of being non-zero, summed over sweeps.  Asynchronous
+ *   viprs_state_bayesr_reset_mean   zeroes both
+ *   viprs_state_bayesr_upload / _download   one of the five buffers, `which` a viprs_bayesr_buffer (created, zeroed, if need be)
+ * REFUSALS, each VIPRS_EINVAL before any launch: a float64 state; a spike-and-slab or grid state; K > 4; a state with SNP groups
+ * or a communicator; no viprs_state_set_n_per_snp; windowed blocks the band kernel cannot take (VIPRS_BAND=0, a window wider than
+ * its q ring, or an upper-form plan); an LD element type outside fp32 / int8 / int16; VIPRS_BAYESR_KEEP_DRAWS, or the sums,
+ * before the draw buffers exist; an unknown flag; null pointers.  A plan without SNPs returns VIPRS_OK.
+ * NOT BUILT: GCTB's --rsq / --p-value filters and its robust parameterisation; K > 4; float64 states; several ranks; a
+ * math_mode = fast variant; row-by-row kernels; windowed blocks in the upper form; per-chromosome hyper-parameters. */
+enum viprs_bayesr_buffer { VIPRS_BAYESR_UNIF = 0, VIPRS_BAYESR_Z = 1, VIPRS_BAYESR_KSTAR = 2, VIPRS_BAYESR_MEAN_SUM = 3,
+                           VIPRS_BAYESR_PIP_SUM = 4, VIPRS_BAYESR_BUFFER_COUNT = 5 };
+#define VIPRS_BAYESR_KEEP_DRAWS 1
+#define VIPRS_BAYESR_MAX_K 4
+int viprs_state_bayesr_draws(viprs_state* state, uint64_t seed, uint64_t draw_index);
+int viprs_state_bayesr_sweep(viprs_state* state, double dq_scale, uint64_t seed, uint64_t draw_index, int flags, int sync);
+int viprs_state_bayesr_sums(viprs_state* state, double* out);
+int viprs_state_bayesr_accumulate(viprs_state* state);
+int viprs_state_bayesr_reset_mean(viprs_state* state);
+int viprs_state_bayesr_upload(viprs_state* state, int which, const void* host);
+int viprs_state_bayesr_download(viprs_state* state, int which, void* host);
+int viprs_bayesr_route(int ld_dtype, int dense, int ragged, int band_ok, int* route);
+int viprs_plan_last_bayesr_draws_ms(viprs_plan* plan, double* ms);
 
 /* ---- LD product: Y = R B over EVERY block of a plan -------------------------------------------------------------------
  * What the reference computes with `ld.dot(B)`: the pseudo-validation metrics against a validation LD panel

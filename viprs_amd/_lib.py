@@ -38,6 +38,10 @@ GIBBS_KEEP_DRAWS = 1
 CS_PSI, CS_DELTA, CS_UB, CS_Z1, CS_Z2, CS_E = range(6)   # viprs_cs_buffer
 CS_KEEP_VARIATES, CS_PREPARE_ONLY = 1, 2
 N_CS_SUMS = 4
+PANEL_BAYESR, BAND_BAYESR = 6, 5                    # ... of the SBayesR route (viprs_bayesr_route)
+BAYESR_UNIF, BAYESR_Z, BAYESR_KSTAR, BAYESR_MEAN_SUM, BAYESR_PIP_SUM = range(5)   # viprs_bayesr_buffer
+BAYESR_KEEP_DRAWS = 1
+BAYESR_MAX_K = 4
 COMM_ID_BYTES = 128
 
 
@@ -147,6 +151,15 @@ _PROTOS = {
     "viprs_state_gibbs_reset_mean": (_i, [_vp]),
     "viprs_gibbs_route": (_i, [_i] * 4 + [ctypes.POINTER(_i)]),
     "viprs_plan_last_gibbs_draws_ms": (_i, [_vp, ctypes.POINTER(_d)]),
+    "viprs_state_bayesr_draws": (_i, [_vp, _u64, _u64]),
+    "viprs_state_bayesr_sweep": (_i, [_vp, _d, _u64, _u64, _i, _i]),
+    "viprs_state_bayesr_sums": (_i, [_vp, _vp]),
+    "viprs_state_bayesr_accumulate": (_i, [_vp]),
+    "viprs_state_bayesr_reset_mean": (_i, [_vp]),
+    "viprs_state_bayesr_upload": (_i, [_vp, _i, _vp]),
+    "viprs_state_bayesr_download": (_i, [_vp, _i, _vp]),
+    "viprs_bayesr_route": (_i, [_i] * 4 + [ctypes.POINTER(_i)]),
+    "viprs_plan_last_bayesr_draws_ms": (_i, [_vp, ctypes.POINTER(_d)]),
     "viprs_state_cs_variates": (_i, [_vp, _u64, _u64, _vp, _i]),
     "viprs_state_cs_update": (_i, [_vp, _i, _vp, _d, _u64, _u64, _i, _i]),
     "viprs_state_cs_sums": (_i, [_vp, _i, _vp, _vp]),
@@ -239,4 +252,11 @@ def gibbs_route(ld_dtype, dense, ragged, band_ok=True):
     """The route of an LDpred2 Gibbs sweep (`viprs_gibbs_route`, include/viprs_hip.h) as a dict over ROUTE_FIELDS; needs no GPU."""
     out = (_i * len(ROUTE_FIELDS))()
     check(lib.viprs_gibbs_route(ld_dtype, int(dense), int(ragged), int(band_ok), out))
+    return dict(zip(ROUTE_FIELDS, out))
+
+
+def bayesr_route(ld_dtype, dense, ragged, band_ok=True):
+    """The route of an SBayesR sweep (`viprs_bayesr_route`, include/viprs_hip.h) as a dict over ROUTE_FIELDS; needs no GPU."""
+    out = (_i * len(ROUTE_FIELDS))()
+    check(lib.viprs_bayesr_route(ld_dtype, int(dense), int(ragged), int(band_ok), out))
     return dict(zip(ROUTE_FIELDS, out))

@@ -123,16 +123,19 @@ int launch_family(viprs_state* S, const EStepArgs<T>& A, int family, int model, 
     } else {
         // (kPanelGridColumn: ONE launch over (block, model) work items, select_model offsets the columns in-kernel)
         // (the elastic-net and Gibbs policies have their own translation units and launchers: launch_panel_enet.inc,
-        //  launch_band_enet.inc, launch_panel_gibbs.inc, launch_band_gibbs.inc)
+        //  launch_band_enet.inc, launch_panel_gibbs.inc, launch_band_gibbs.inc; SBayesR likewise: launch_panel_bayesr.inc,
+        //  launch_band_bayesr.inc)
         if (family == kFamPanel)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
                 return model == kPanelElasticNet ? launch_panel_enet<decltype(u)>(P, A)
                        : model == kPanelGibbs    ? launch_panel_gibbs<decltype(u)>(P, A)
+                       : model == kPanelBayesR   ? launch_panel_bayesr<decltype(u)>(P, A)
                                                  : launch_panel<decltype(u)>(P, A, model); });
         if (family == kFamBand)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kBandLdTypeError, [&](auto u) {
                 return model == kBandElasticNet ? launch_band_enet<decltype(u)>(P, A)
                        : model == kBandGibbs    ? launch_band_gibbs<decltype(u)>(P, A)
+                       : model == kBandBayesR   ? launch_band_bayesr<decltype(u)>(P, A)
                                                 : launch_band<decltype(u)>(P, A, model); });
         if (family == kFamGridBatched)
             return for_ld_type<float, int8_t, int16_t>(P->ld_dtype, kDenseLdTypeError, [&](auto u) {
@@ -397,6 +400,45 @@ int viprs_gibbs_route(int ld_dtype, int dense, int ragged, int band_ok, int* rou
     SweepRoute r;
     std::string err;
     const int rc = gibbs_route(ld_dtype, dense != 0, ragged != 0, band_ok != 0, r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    route_fields(r, route);
+    return VIPRS_OK;
+}
+
+// The sweep of SBayesR (panel_bayesr.h; the rest of its calls: abi_bayesr.hip).  It lives here because it is executed by
+// run_route like every other sweep: a mixture state runs with n_active == 0, and the `active` slot, which nothing then reads
+// but the policy, carries the state's draw allocation.
+int viprs_state_bayesr_sweep(viprs_state* S, double dq_scale, uint64_t seed, uint64_t draw_index, int flags, int sync) {
+    // every refusal comes before the first launch
+    int rc = bayesr_state_check(S, "SBayesR sweep");
+    if (rc != VIPRS_OK) return rc;
+    if (flags & ~VIPRS_BAYESR_KEEP_DRAWS) return fail(VIPRS_EINVAL, "SBayesR sweep: unknown flag");
+    const bool keep = (flags & VIPRS_BAYESR_KEEP_DRAWS) != 0;
+    viprs_plan* P = S->plan;
+    if (keep && !S->d_bayesr.p && P->m > 0)
+        return fail(VIPRS_EINVAL, "SBayesR sweep: VIPRS_BAYESR_KEEP_DRAWS before the draw buffers exist (no draws call, sweep or "
+                                  "upload yet)");
+    SweepRoute r;
+    std::string err;
+    // (the band kernel of this policy exists for the symmetric form only: launch_band_bayesr.inc)
+    rc = bayesr_route(P->ld_dtype, !P->dense_h.empty(), !P->ragged_h.empty(), band_ok(P) && P->low_memory == 0, r, err);
+    if (rc != VIPRS_OK) return fail(rc, err);
+    if (P->m == 0) return VIPRS_OK;
+    HIP_TRY(hipSetDevice(P->device));
+    rc = keep ? VIPRS_OK : bayesr_enqueue_draws(S, seed, draw_index);
+    if (rc != VIPRS_OK) return rc;
+    if (!S->d_bayesr.p) return fail(VIPRS_EDEVICE, "SBayesR sweep: no draw buffers");
+    rc = run_route(S, r, dq_scale, reinterpret_cast<const int32_t*>(S->d_bayesr.p), 0);
+    if (rc != VIPRS_OK) return rc;
+    if (sync) HIP_TRY(hipStreamSynchronize(P->stream));
+    return VIPRS_OK;
+}
+
+int viprs_bayesr_route(int ld_dtype, int dense, int ragged, int band_ok, int* route) {
+    if (!route) return fail(VIPRS_EINVAL, "null argument");
+    SweepRoute r;
+    std::string err;
+    const int rc = bayesr_route(ld_dtype, dense != 0, ragged != 0, band_ok != 0, r, err);
     if (rc != VIPRS_OK) return fail(rc, err);
     route_fields(r, route);
     return VIPRS_OK;

@@ -307,6 +307,7 @@ struct viprs_plan {
     viprs::RidgeWork ridge;                        // viprs_plan_solve_ridge
     viprs::EventBracket time_gibbs_draws;          // the draws kernel of the Gibbs sweeps (abi_gibbs.hip)
     viprs::EventBracket time_cs_variates, time_cs_update;   // the two PRS-CS kernels (abi_cs.hip)
+    viprs::EventBracket time_bayesr_draws;         // the draws kernel of the SBayesR sweeps (abi_bayesr.hip)
     viprs::SpectrumWork spectrum;                  // viprs_plan_extremal_eigenvalues
     viprs::SusieWork susie;                        // viprs_plan_susie
 
@@ -356,6 +357,12 @@ struct viprs_state {
     // viprs_cs_buffer in ONE allocation, in the order of the enum; the (column, sigma2, phi) rows of the call in flight
     viprs::DevBuf<float> d_cs;
     viprs::DevBuf<double> d_cs_rows;
+    // SBayesR (abi_bayesr.hip), allocated by the first SBayesR call: 3 m four-byte words in ONE allocation -- U, z (float32),
+    // then k* (int32); the two (m,) float64 accumulators, mean_sum then pip_sum, created on first use; partials and results of
+    // viprs_state_bayesr_sums
+    viprs::DevBuf<float> d_bayesr;
+    viprs::DevBuf<double> d_bayesr_acc;
+    viprs::DevBuf<double> d_bayesr_sums;
     ~viprs_state() {
         if (h_sums) (void)hipHostFree(h_sums);
         if (h_rows) (void)hipHostFree(h_rows);
@@ -442,6 +449,15 @@ template <typename U> int launch_band_gibbs(viprs_plan* P, EStepArgs<float> A);
 int gibbs_ensure_draws(viprs_state* S);
 int gibbs_enqueue_draws(viprs_state* S, uint64_t seed, uint64_t draw_index, const int32_t* d_active, int n_active);
 const float* gibbs_draws_slot(const viprs_state* S);
+// the SBayesR policy (panel_bayesr.h): panel_bayesr_*.hip, band_bayesr_*.hip
+template <typename U> int launch_panel_bayesr(viprs_plan* P, EStepArgs<float> A);
+template <typename U> int launch_band_bayesr(viprs_plan* P, EStepArgs<float> A);
+// abi_bayesr.hip: what every SBayesR entry point refuses (`what` names the call in the message), the state's draw allocation
+// (U | z | k*, zeroed, created by the first SBayesR call) and the draws kernel on the plan's stream between the plan's own two
+// events (nothing is synchronised).  A sweep hands the policy the allocation in the `active` slot of its arguments.
+int bayesr_state_check(const viprs_state* S, const char* what);
+int bayesr_ensure_draws(viprs_state* S);
+int bayesr_enqueue_draws(viprs_state* S, uint64_t seed, uint64_t draw_index);
 // abi_cs.hip: what every PRS-CS entry point refuses (`what` names the call in the message), and the state's cs buffers
 // (psi = 1, the rest zero), created by the first call that needs them
 int cs_state_check(const viprs_state* S, const char* what);

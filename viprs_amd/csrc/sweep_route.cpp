@@ -95,4 +95,27 @@ int gibbs_route(int ld_dtype, bool dense, bool ragged, bool band_ok, SweepRoute&
     return VIPRS_OK;
 }
 
+int bayesr_route(int ld_dtype, bool dense, bool ragged, bool band_ok, SweepRoute& r, std::string& err) {
+    r = SweepRoute{};
+    if (ragged && !band_ok) {
+        err = "SBayesR sweep: windowed LD blocks the band kernel cannot take (VIPRS_BAND=0, a window wider than its q ring, or "
+              "the upper-triangular form: build the plan in the symmetric form, low_memory = 0 / SBayesR(low_memory=False)): there is "
+              "no row-by-row kernel for this update";
+        return VIPRS_EINVAL;
+    }
+    if (dense) { r.dense_family = kFamPanel; r.dense_model = kPanelBayesR; }
+    if (ragged) { r.ragged_family = kFamBand; r.ragged_model = kBandBayesR; }
+    // as sweep_route's mixture row
+    r.prologue = !(dense && !ragged);
+    r.prologue_per_model = false;
+    r.start_event_by_launcher = dense;
+    r.whole_sweep_events = false;
+    r.dense_bracketed = true;
+
+    const bool three = ld_dtype == VIPRS_LD_F32 || ld_dtype == VIPRS_LD_I8 || ld_dtype == VIPRS_LD_I16;
+    if (!three && dense) { err = kDenseLdTypeError; return VIPRS_EINVAL; }
+    if (!three && ragged) { err = kBandLdTypeError; return VIPRS_EINVAL; }
+    return VIPRS_OK;
+}
+
 }  // namespace viprs

@@ -10,8 +10,9 @@ namespace viprs {
 // ---- kernel families (one translation unit per family and LD element type) and their model constants -------------
 enum { kFamNone = 0, kFamGeneric = 1, kFamTileF64 = 2, kFamPanel = 3, kFamBand = 4, kFamGridBatched = 5 };   // viprs_sweep_family
 enum { kGenSpikeSlab = 0, kGenMixture = 1, kGenGrid = 2 };          // = viprs_model_kind; the tile_f64 kernels take them too
-enum { kPanelSpikeSlab = 0, kPanelGridColumn = 1, kPanelMixture = 2, kPanelMixtureWide = 3, kPanelElasticNet = 4, kPanelGibbs = 5 };
-enum { kBandSpikeSlab = 0, kBandGridColumn = 1, kBandMixture = 2, kBandElasticNet = 3, kBandGibbs = 4 };
+enum { kPanelSpikeSlab = 0, kPanelGridColumn = 1, kPanelMixture = 2, kPanelMixtureWide = 3, kPanelElasticNet = 4, kPanelGibbs = 5,
+       kPanelBayesR = 6 };
+enum { kBandSpikeSlab = 0, kBandGridColumn = 1, kBandMixture = 2, kBandElasticNet = 3, kBandGibbs = 4, kBandBayesR = 5 };
 
 // the launchers' own words for an LD element type they have no instantiation for
 constexpr const char* kDenseLdTypeError = "dense schedule with unsupported LD dtype";
@@ -62,5 +63,12 @@ int enet_route(bool grid, int ld_dtype, bool dense, bool ragged, bool band_ok, S
 // kBandGibbs for the windowed ones, the columns as (block, model) items, with the prologue and the events of the grid row of
 // sweep_route.  Refusals as enet_route's, in its own words.
 int gibbs_route(int ld_dtype, bool dense, bool ragged, bool band_ok, SweepRoute& r, std::string& err);
+
+// The route of an SBayesR sweep (viprs_state_bayesr_sweep) of an fp32 mixture state of K <= 4 components: kPanelBayesR for the
+// dense blocks, kBandBayesR for the windowed ones, with the prologue and the events of the mixture row of sweep_route.
+// Refusals, each VIPRS_EINVAL: windowed blocks the band kernel cannot take (`band_ok` false: for this sweep that includes
+// every upper-form plan, whose band instantiation is not shipped); an LD element type outside the shipped ones (fp32 /
+// int8 / int16), with the launcher's message.
+int bayesr_route(int ld_dtype, bool dense, bool ragged, bool band_ok, SweepRoute& r, std::string& err);
 
 }  // namespace viprs

@@ -431,6 +431,12 @@ class LDPlan:
         L.check(L.lib.viprs_plan_last_gibbs_draws_ms(self.handle, ctypes.byref(ms)))
         return ms.value
 
+    def last_bayesr_draws_ms(self):
+        """Event time (ms) of the last SBayesR draws kernel (`viprs_plan_last_bayesr_draws_ms`)."""
+        ms = ctypes.c_double()
+        L.check(L.lib.viprs_plan_last_bayesr_draws_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     def last_cs_ms(self):
         """Event times (ms) of the last PRS-CS variates kernel and of the last update kernel on this plan
         (`viprs_plan_last_cs_ms`; 0 for one that has not run)."""
@@ -1058,6 +1064,49 @@ class DeviceState:
         if a.dtype != np.float32 or a.shape != (self.plan.m, self.width) or not a.flags.f_contiguous:
             raise ValueError(f"{which}: a Fortran-contiguous float32 array of shape {(self.plan.m, self.width)}")
         L.check(L.lib.viprs_state_cs_upload(self._h, self._CS[which], _ptr(a)))
+
+    # -- SBayesR: a mixture Gibbs draw where the mixture E-step takes an expectation -------------------------
+    _BAYESR = {"unif": (L.BAYESR_UNIF, np.float32), "z": (L.BAYESR_Z, np.float32), "kstar": (L.BAYESR_KSTAR, np.int32),
+               "mean_sum": (L.BAYESR_MEAN_SUM, np.float64), "pip_sum": (L.BAYESR_PIP_SUM, np.float64)}
+
+    def bayesr_draws(self, seed, draw_index):
+        """``U`` and ``z`` of every SNP of a float32 mixture state (`viprs_state_bayesr_draws`, include/viprs_hip.h;
+        `viprs_amd.stats.bayesr.bayesr_draws_host`): a function of (seed, draw_index, SNP)."""
+        L.check(L.lib.viprs_state_bayesr_draws(self._h, int(seed), int(draw_index)))
+
+    def bayesr_sweep(self, dq_scale=1.0, seed=0, draw_index=0, keep_draws=False, sync=True):
+        """One SBayesR sweep (`viprs_state_bayesr_sweep`; `viprs_amd.stats.bayesr`) of a float32 mixture state of K <= 4
+        components prepared by `prep_mixture` with lambda = 0: fresh draws, or -- `keep_draws` -- whatever the buffers hold."""
+        L.check(L.lib.viprs_state_bayesr_sweep(self._h, float(dq_scale), int(seed), int(draw_index),
+                                               L.BAYESR_KEEP_DRAWS if keep_draws else 0, int(bool(sync))))
+
+    def bayesr_sums(self):
+        """``2 K + 4`` float64: the number of SNPs with k* = 0 .. K, sum eta^2 over k* = k for k = 1 .. K, sum q eta,
+        sum eta^2, sum std_beta eta (`viprs_state_bayesr_sums`)."""
+        out = np.zeros(2 * self.width + 4, dtype=np.float64)
+        L.check(L.lib.viprs_state_bayesr_sums(self._h, _ptr(out)))
+        return out
+
+    def bayesr_accumulate(self):
+        """``mean_sum += sum_k gamma_k mu_k`` and ``pip_sum += sum_k gamma_k`` (`viprs_state_bayesr_accumulate`)."""
+        L.check(L.lib.viprs_state_bayesr_accumulate(self._h))
+
+    def bayesr_reset_mean(self):
+        L.check(L.lib.viprs_state_bayesr_reset_mean(self._h))
+
+    def bayesr_download(self, which):
+        """``"unif"`` / ``"z"`` (float32), ``"kstar"`` (int32), ``"mean_sum"`` / ``"pip_sum"`` (float64): ``(m,)``."""
+        code, dt = self._BAYESR[which]
+        out = np.zeros(self.plan.m, dtype=dt)
+        L.check(L.lib.viprs_state_bayesr_download(self._h, code, _ptr(out)))
+        return out
+
+    def bayesr_upload(self, which, array):
+        code, dt = self._BAYESR[which]
+        a = np.asarray(array)
+        if a.dtype != dt or a.shape != (self.plan.m,) or not a.flags.c_contiguous:
+            raise ValueError(f"{which}: a contiguous {np.dtype(dt).name} array of shape {(self.plan.m,)}")
+        L.check(L.lib.viprs_state_bayesr_upload(self._h, code, _ptr(a)))
 
     def dot(self, name="eta", dq_scale=1.0, include_diagonal=True):
         """``R @ eta`` with the resident posterior mean as `B` (`viprs_state_dot`): only the ``m x n_cols`` results cross to
