@@ -219,6 +219,23 @@ def test_lassosum_fit_equals_the_host_fit(gpu):
     assert {c: b.shape for c, b in got.post_mean_beta.items()} == {c: (n,) for c, n in got.shapes.items()}
 
 
+def test_from_plan_equals_the_loader_fit(gpu):
+    """`Lassosum.from_plan` on the plan a loader-built model made (one chromosome of [130, 64] SNPs, int8 LD): the same fit."""
+    from viprs_amd.data import ArrayDataLoader
+    from viprs_amd.model import Lassosum
+    kw = dict(s=ER.MODEL_S, lambdas=ER.MODEL_LAMBDAS, tol=ER.MODEL_TOL)
+    gdl = ArrayDataLoader.synthetic({1: [130, 64]}, ld_dtype=np.int8, n=5e4, kind="longrange", h2=0.5)
+    a = Lassosum(gdl, dequantize_on_the_fly=True, **kw)
+    b = Lassosum.from_plan(a._plan, a.std_beta[1], a.dequantize_scale, **kw)
+    a.fit()
+    b.fit()
+    assert np.array_equal(a.post_mean_beta[1], b.post_mean_beta[1], equal_nan=True)
+    assert a.post_mean_beta[1].shape == (194, 6) and a.post_mean_beta[1].any()
+    assert list(a.grid_table.columns) == list(b.grid_table.columns)
+    for k in a.grid_table.columns:
+        assert np.array_equal(a.grid_table[k].to_numpy(), b.grid_table[k].to_numpy(), equal_nan=k == "objective"), k
+
+
 def _too_wide_a_band():
     """One windowed component whose first row reaches 16 400 SNPs: 257 panels to the right, more than the q ring holds."""
     m, reach = 16500, 16400

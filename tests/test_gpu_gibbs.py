@@ -305,6 +305,21 @@ def test_ldpred2_fit_equals_the_host_fit(gpu, mode):
         assert r.shape == (3,) and dev.best_model_idx == int(np.argmax(r)) and r.max() > 0
 
 
+def test_from_plan_equals_the_loader_fit(gpu):
+    """`LDpred2.from_plan` on the plan a loader-built model made (one chromosome of [130, 64] SNPs, int8 LD): the same fit."""
+    from viprs_amd.model import LDpred2
+    kw = dict(mode="auto", n_chains=3, burn_in=4, num_iter=4, seed=5)
+    a = LDpred2(GR.model_gdl({1: [130, 64]}), h2_init=0.3, dequantize_on_the_fly=True, **kw)
+    b = LDpred2.from_plan(a._plan, a.std_beta[1], a._n_per_snp, a.dequantize_scale, 0.3, **kw)
+    a.fit()
+    b.fit()
+    assert np.array_equal(a.post_mean_beta[1], b.post_mean_beta[1], equal_nan=True) and a.post_mean_beta[1].any()
+    assert list(a.grid_table.columns) == list(b.grid_table.columns) == ["p", "h2", "diverged", "n_nonzero", "kept"]
+    for k in a.grid_table.columns:
+        assert np.array_equal(a.grid_table[k].to_numpy(), b.grid_table[k].to_numpy(), equal_nan=k in ("p", "h2")), k
+    assert np.array_equal(a.p_history, b.p_history, equal_nan=True) and b.p_history.shape == (8, 3)
+
+
 @pytest.mark.parametrize("case", ["float64", "spike_slab", "mixture", "masked_grid", "wide_band", "keep_draws_first"])
 def test_refusals_launch_nothing(gpu, case):
     """Each refusal is a ValueError (VIPRS_EINVAL) before any launch: the timing record does not move, the state's fields

@@ -84,6 +84,7 @@ def log(monkeypatch):
             assert isinstance(data, np.ndarray) and data.ndim == 1 and data.flags.c_contiguous
             assert int(ip[-1]) == data.shape[0]
             self.m, self.low_memory, self.ld_dtype, self.closed = m, bool(low_memory), data.dtype, False
+            self.indptr, self.data = ip, data
             events.append(("plan", ctor, bool(low_memory), data.dtype.name, int(data.shape[0]), m))
 
         def close(self):
@@ -233,16 +234,55 @@ def test_viprs_e_step_fn_mirrors_the_upper_store_on_the_host(log):
     assert [v.ld_data[c].shape[0] for c in (1, 2)] == [NNZ["symmetric"][1], NNZ["symmetric"][2]]
 
 
+# ---- the seven models on one merged plan -------------------------------------------------------------------------------
+# class name, the hook that puts it on the host path, further arguments, the error without a HIP device (literal: copied from
+# the constructors before they shared `MergedPlanModel._load`), `_ld` kept beside a plan, has `_n_per_snp`
+def _hooks():
+    from viprs_amd.stats import clump, enet, gibbs, susie
+    return dict(clump=clump.clump_host, enet=enet.enet_sweep_host, gibbs=gibbs.gibbs_sweep_host, susie=susie.susie_host)
+
+
+MERGED_MODELS = [
+    ("ClumpThreshold", dict(clump_fn="clump"), {},
+     "ClumpThreshold needs a HIP device (viprs_amd.stats.clump.clump runs on the host)", False, False),
+    ("LDPredInf", dict(solve_fn=_no_device_fn), dict(h2=0.3),
+     "LDPredInf needs a HIP device: the solve has no CPU fallback", False, False),
+    ("Lassosum", dict(sweep_fn="enet"), {},
+     "Lassosum needs a HIP device (viprs_amd.stats.enet.enet_sweep_host is the sweep on the host: pass it as sweep_fn)",
+     False, False),
+    ("LDpred2", dict(sweep_fn="gibbs"), dict(h2_init=0.3),
+     "LDpred2 needs a HIP device (viprs_amd.stats.gibbs.gibbs_sweep_host is the sweep on the host: pass it as sweep_fn)",
+     False, True),
+    ("PRSCS", dict(sweep_fn="gibbs"), {},
+     "PRSCS needs a HIP device (viprs_amd.stats.gibbs.gibbs_sweep_host is the sweep on the host: pass it as sweep_fn)",
+     False, True),
+    ("SBayesR", dict(backend="host"), dict(h2_init=0.3),
+     "SBayesR needs a HIP device (backend='host' runs viprs_amd.stats.bayesr on the CPU)", False, True),
+    ("SuSiE", dict(fit_fn="susie"), {},
+     "SuSiE needs a HIP device: pass fit_fn=viprs_amd.stats.susie.susie_host for a host fit", True, False),
+]
+MERGED_CHROMS = {1: [130, 64], 2: [200, 1]}                 # the loader of the model tests: 194 + 201 = 395 SNPs
+MERGED_NNZ = {True: 8385 + 2016 + 19900 + 0, False: 130 ** 2 + 64 ** 2 + 200 ** 2 + 1}     # by `low_memory`
+
+
+def _merged_model(name, low_memory=True, hook=None, gdl=None, **kw):
+    import viprs_amd.model as models
+    if gdl is None:
+        gdl = ArrayDataLoader.synthetic(MERGED_CHROMS, ld_dtype=np.int8, n=5e4, kind="longrange", h2=0.5)
+    hook = {k: _hooks().get(v, v) if isinstance(v, str) else v for k, v in (hook or {}).items()}     # ("host" stays "host")
+    return getattr(models, name)(gdl, low_memory=low_memory, dequantize_on_the_fly=True, **hook, **kw)
+
+
 # ---- the mixed loader: chromosome 1 stored in float32, chromosome 2 in int8, dequantize_on_the_fly=True ----------------
 def test_mixed_stored_dtypes(log):
-    """`VIPRS` and `LDPredInf` thread `dequantize_on_the_fly` through the chromosomes in sorted order: the float-stored
-    first chromosome turns it off for the int8 one after it.  `ld_scores` decides per matrix."""
+    """`VIPRS` and the seven models on a merged plan (`LDPredInf` with ``h2=0.3`` and `solve_fn` among them) thread
+    `dequantize_on_the_fly` through the chromosomes in sorted order: the float-stored first chromosome turns it off for the
+    int8 one after it.  `ld_scores` decides per matrix."""
     from viprs_amd.model import VIPRS
-    from viprs_amd.model.LDPredInf import LDPredInf
     from viprs_amd.stats.ldsc import ld_scores, ld_scores_host
     mixed = {1: "float32", 2: "int8"}
-    for make in (lambda g: VIPRS(g, dequantize_on_the_fly=True, e_step_fn=_no_device_fn),
-                 lambda g: LDPredInf(g, h2=0.3, dequantize_on_the_fly=True, solve_fn=_no_device_fn)):
+    for make in [lambda g: VIPRS(g, dequantize_on_the_fly=True, e_step_fn=_no_device_fn)] + [
+            lambda g, r=r: _merged_model(r[0], hook=r[1], gdl=g, **r[2]) for r in MERGED_MODELS]:
         del log[:]
         model = make(_loader(log, stored=mixed))
         assert log == [("load", 1, False, "float32"), ("load", 2, False, "float32")]
@@ -289,6 +329,59 @@ def test_ldpredinf_constructor_loads_and_plans(log, row, host):
     if host:
         lb, ip, data = model._ld
         assert (lb.dtype, data.dtype.name, data.shape[0], lb.shape[0]) == (np.int32,) + plan[3:]
+
+
+# ---- the seven models on one merged plan: the constructors --------------------------------------------------------------
+@pytest.mark.parametrize("low_memory", [True, False], ids=["upper", "symmetric"])
+@pytest.mark.parametrize("row", MERGED_MODELS, ids=[r[0] for r in MERGED_MODELS])
+def test_merged_plan_models_load_once_and_open_one_plan(log, monkeypatch, row, low_memory):
+    """Each of the seven constructors, on its host path and on a recorded plan: one plan over the merged arrays of both
+    chromosomes in the form `low_memory` implies; `_ld`, `device`, `_seg`, `std_beta` (`SuSiE`: `z`) and `_n_per_snp`; and
+    without a HIP device its own RuntimeError before any plan."""
+    name, hook, kw, no_device, keeps_ld, has_n = row
+    host = _merged_model(name, low_memory, hook, **kw)
+    assert not _of(log, "plan") and host._plan is None and not hasattr(host, "device")
+    lb, ip, data = host._ld
+    assert (lb.dtype, lb.shape, ip.shape, data.dtype, data.shape) == (np.int32, (395,), (396,), np.int8, (MERGED_NNZ[low_memory],))
+    dev = _merged_model(name, low_memory, **kw)
+    assert _of(log, "plan") == [("plan", "LDPlan", low_memory, "int8", MERGED_NNZ[low_memory], 395)]
+    assert dev.device == 0 and dev._plan.m == 395 and dev._plan.low_memory is low_memory
+    assert np.array_equal(dev._plan.indptr, ip) and np.array_equal(dev._plan.data, data)      # (the merged arrays)
+    if keeps_ld:
+        assert dev._ld[1] is dev._plan.indptr and dev._ld[2] is dev._plan.data
+    else:
+        assert getattr(dev, "_ld", None) is None
+    for model in (host, dev):
+        assert model._seg == {1: (0, 194), 2: (194, 395)} and model.shapes == {1: 194, 2: 201} and model.m == 395
+        assert model.low_memory is low_memory and model.dequantize_on_the_fly is True and model.dequantize_scale == 1.0 / 127
+        assert model.float_precision == "float32" and model._T == np.float32
+        per_snp = model.z if name == "SuSiE" else model.std_beta
+        assert hasattr(model, "std_beta") is (name != "SuSiE") and hasattr(model, "_sqrt_n") is (name == "SuSiE")
+        assert {c: (a.shape, a.dtype) for c, a in per_snp.items()} == {
+            c: ((n,), np.dtype(np.float64 if name == "SuSiE" else np.float32)) for c, n in ((1, 194), (2, 201))}
+        assert hasattr(model, "_n_per_snp") is has_n
+        if has_n:
+            assert model._n_per_snp.shape == (395,) and model._n_per_snp.dtype == np.float64
+    for c in (1, 2):
+        assert np.array_equal(host.z[c] if name == "SuSiE" else host.std_beta[c], dev.z[c] if name == "SuSiE" else dev.std_beta[c])
+    del log[:]
+    monkeypatch.setattr(_lib, "device_count", lambda: 0)
+    with pytest.raises(RuntimeError) as e:
+        _merged_model(name, low_memory, **kw)
+    assert str(e.value) == no_device and not _of(log, "plan")
+
+
+def test_split_and_concat_are_inverses():
+    model = _merged_model("ClumpThreshold", True, dict(clump_fn="clump"))
+    rng = np.random.default_rng(0)
+    d = {1: rng.normal(size=194), 2: rng.normal(size=201)}
+    D = {1: rng.normal(size=(194, 3)).astype(np.float32), 2: rng.normal(size=(201, 3)).astype(np.float32)}
+    for per_chromosome in (d, D):
+        whole = model._concat(per_chromosome)
+        assert whole.shape[0] == 395 and whole.dtype == per_chromosome[1].dtype
+        back = model._split(whole)
+        assert list(back) == [1, 2] and all(np.array_equal(back[c], per_chromosome[c]) for c in (1, 2))
+        assert not any(np.shares_memory(back[c], whole) for c in (1, 2))
 
 
 # ---- ld_scores ---------------------------------------------------------------------------------------------------------

@@ -14,7 +14,8 @@ Reported per kind: median, min and max in ms; per dtype the ratios of the median
 spike-and-slab sweeps' own (max - min) / median.
 
 `fit`: `Lassosum.fit()` with the default 4 x 20 grid on the same plan (int8 LD unless --fit-ld says otherwise): wall time,
-sweeps per lambda and column, total sweeps.  The model is put on the device-generated plan directly (no LD on the host).
+sweeps per lambda and column, total sweeps.  The model is put on the device-generated plan directly (`Lassosum.from_plan`; no
+LD on the host).
 `host`: the C replay of the sweep (tests/enet_replay.c, one core) on --host-config (cfg2: 19 k SNPs), ms per sweep.
 """
 import argparse
@@ -100,18 +101,7 @@ def sweep_times(plan, skel, inp, rounds, per_round):
 def fit_on_plan(plan, skel, std_beta):
     """`Lassosum.fit()` with the default grid on a plan that exists on the device only."""
     from viprs_amd.model import Lassosum
-    from viprs_amd.stats.enet import lambda_path
-
-    class _Loader:
-        m = plan.m
-    model = Lassosum.__new__(Lassosum)
-    model.gdl, model.shapes, model._seg = _Loader, {1: plan.m}, {1: (0, plan.m)}
-    model.s, model.lambdas = np.array([0.2, 0.5, 0.9, 1.0]), lambda_path()
-    model.penalty_factor = np.ones(plan.m)
-    model.tol, model.max_sweeps, model.low_memory = 1e-4, 1000, True
-    model._T, model._sweep_fn, model._plan, model._ld = np.dtype(np.float32), None, plan, None
-    model.dequantize_scale, model.std_beta = skel.dq_scale, {1: std_beta}
-    model.n_models = 80
+    model = Lassosum.from_plan(plan, std_beta, skel.dq_scale)
     t0 = time.perf_counter()
     model.fit()
     wall = time.perf_counter() - t0

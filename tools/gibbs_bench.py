@@ -15,7 +15,8 @@ which = 0: the draws kernel is outside them), the draws kernel's is `viprs_plan_
 median, min and max in ms; the ratios of the Gibbs medians to the elastic-net and the grid-column medians of the same width.
 
 `fit`: `LDpred2(mode="auto")` with `--chains` chains, 20 + 10 iterations, on the same plan (int8 LD unless --fit-ld says
-otherwise): wall time per iteration.  The model is put on the device-generated plan directly (no LD on the host).
+otherwise): wall time per iteration.  The model is put on the device-generated plan directly (`LDpred2.from_plan`; no LD on
+the host).
 """
 import argparse
 import json
@@ -102,18 +103,8 @@ def auto_on_plan(plan, skel, ss, std_beta, chains, burn_in=20, num_iter=10):
     """`LDpred2(mode="auto").fit()` on a plan that exists on the device only."""
     from viprs_amd.model import LDpred2
 
-    class _Loader:
-        m = plan.m
-    model = LDpred2.__new__(LDpred2)
-    model.gdl, model.shapes, model._seg = _Loader, {1: plan.m}, {1: (0, plan.m)}
-    model.mode, model.burn_in, model.num_iter, model.seed, model.n_chains = "auto", burn_in, num_iter, 1, chains
-    model.low_memory, model._T, model._sweep_fn, model._draws_fn = True, np.dtype(np.float32), None, None
-    model._keep_draws_log, model.draws_log, model._plan, model._ld = False, [], plan, None
-    model.dequantize_scale, model.std_beta, model._n_per_snp = skel.dq_scale, {1: std_beta}, np.asarray(ss.n_per_snp, dtype=np.float64)
-    model.h2_init = 0.2
-    model.chain_p = np.exp(np.linspace(np.log(1e-4), np.log(0.2), chains))
-    model.chain_h2 = np.full(chains, model.h2_init)
-    model.n_models = 1
+    model = LDpred2.from_plan(plan, std_beta, ss.n_per_snp, skel.dq_scale, 0.2, mode="auto", burn_in=burn_in, num_iter=num_iter,
+                              n_chains=chains, seed=1)
     t0 = time.perf_counter()
     model.fit()
     wall = time.perf_counter() - t0

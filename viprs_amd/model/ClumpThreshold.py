@@ -15,11 +15,10 @@ the results follows its grid models (``post_mean_beta[c]`` of shape ``(m_c, n_mo
 """
 import numpy as np
 
-from ..data import merge_ld_arrays
-from ._ld_loading import LoadedLD, ld_form, load_ld_in_order, open_plan
+from ._merged_plan import MergedPlanModel
 
 
-class ClumpThreshold:
+class ClumpThreshold(MergedPlanModel):
 
     def __init__(self, gdl, r2=(0.1, 0.2, 0.5, 0.8), p_thresholds=(5e-8, 1e-6, 1e-4, 1e-3, 1e-2, 0.05, 0.1, 0.5, 1.0),
                  float_precision="float32", low_memory=True, dequantize_on_the_fly=False, device=None, clump_fn=None,
@@ -35,59 +34,22 @@ class ClumpThreshold:
         :param clump_fn: test hook -- a callable with `viprs_amd.stats.clump.clump_host`'s signature that replaces the
             device clumping.
         """
-        if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
-            raise AssertionError("The data loader must contain summary statistics and LD matrices.")
-        if comm is not None and comm.world_size > 1:
-            raise NotImplementedError("ClumpThreshold runs on one rank only (world_size > 1: the clumping is not sharded)")
+        self._set_loader(gdl, comm, not_sharded="clumping")
         self.r2 = np.atleast_1d(np.asarray(r2, dtype=np.float64))
         self.p_thresholds = np.atleast_1d(np.asarray(p_thresholds, dtype=np.float64))
         if self.r2.ndim != 1 or not 1 <= self.r2.shape[0] <= 32 or not np.all(np.isfinite(self.r2)) or np.any(self.r2 < 0):
             raise ValueError("r2: 1..32 finite thresholds >= 0")
         if self.p_thresholds.ndim != 1 or self.p_thresholds.shape[0] < 1 or np.any(~(self.p_thresholds > 0)):
             raise ValueError("p_thresholds: at least one threshold, each > 0")
-        self.gdl = gdl
-        self.float_precision = float_precision
-        self._T = np.dtype(float_precision)
-        self.low_memory = bool(low_memory)
         self._clump_fn = clump_fn
-        self.shapes = {c: int(s) for c, s in gdl.shapes.items()}
-        chroms = self.chromosomes
-        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
-            gdl.get_ld_matrices(), chroms, self.low_memory, dequantize_on_the_fly, float_precision, expand_ld_on_device=False)
-        self.std_beta = {c: np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T) for c in chroms}
-        # one plan over the concatenated chromosomes (LD blocks never span chromosomes)
-        lb, ip, data, self._seg = merge_ld_arrays(
-            chroms, self.shapes, {c: ld.left_bound for c, ld in loaded.items()}, {c: ld.indptr for c, ld in loaded.items()},
-            {c: ld.data for c, ld in loaded.items()})
-        del loaded
-        self._plan = None
-        if clump_fn is None:
-            from .. import _lib
-            if _lib.device_count() < 1:
-                raise RuntimeError("ClumpThreshold needs a HIP device (viprs_amd.stats.clump.clump runs on the host)")
-            self.device = int(device) if device is not None else 0
-            self._plan = open_plan(LoadedLD(lb, ip, data, ld_form(self.low_memory)), self.device)
-        else:
-            self._ld = (lb, ip, data)
+        self._load(float_precision, low_memory, dequantize_on_the_fly, device, clump_fn is not None,
+                   "ClumpThreshold needs a HIP device (viprs_amd.stats.clump.clump runs on the host)")
         self.n_models = int(self.r2.shape[0] * self.p_thresholds.shape[0])
         self.index_of = None
         self.post_mean_beta = None
         self.grid_table = None
         self.validation_result = None
         self.best_model_idx = None
-
-    @property
-    def chromosomes(self):
-        return sorted(self.shapes)
-
-    @property
-    def m(self):
-        return int(self.gdl.m)
-
-    n_snps = m
-
-    def get_posterior_mean_beta(self):
-        return self.post_mean_beta
 
     def _chisq(self):
         from ..stats.ldsc import chisq_statistic
@@ -108,26 +70,20 @@ class ClumpThreshold:
             index_of = self._plan.clump(order, self.r2, dq_scale=self.dequantize_scale)
         index_of = np.asarray(index_of).reshape(self.m, self.r2.shape[0])
         is_index = index_of == np.arange(self.m, dtype=index_of.dtype)[:, None]
-        b = np.concatenate([self.std_beta[c] for c in self.chromosomes])
+        b = self._concat(self.std_beta)
         n_p = cuts.shape[0]
         beta = np.zeros((self.m, self.n_models), dtype=self._T)
         for g in range(self.r2.shape[0]):
             for t in range(n_p):
                 keep = is_index[:, g] & (chisq >= cuts[t])
                 beta[keep, g * n_p + t] = b[keep]
-        self.index_of = {c: np.array(index_of[a:e]) for c, (a, e) in self._seg.items()}
-        self.post_mean_beta = {c: np.array(beta[a:e]) for c, (a, e) in self._seg.items()}
+        self.index_of = self._split(index_of)
+        self.post_mean_beta = self._split(beta)
         self.grid_table = pd.DataFrame({"r2": np.repeat(self.r2, n_p), "p_threshold": np.tile(self.p_thresholds, self.r2.shape[0]),
                                         "n_snps": np.count_nonzero(beta, axis=0)})
         self.validation_result = self.grid_table.copy()
         self.best_model_idx = None
         return self
-
-    def predict(self, test_gdl=None, **kw):
-        """Polygenic scores of the training loader's genotyped samples, or of `test_gdl`'s, ``(n, n_models)`` (``(n,)`` after
-        `select_best`): `viprs_amd.genotypes.model_predict`."""
-        from ..genotypes import model_predict
-        return model_predict(self, test_gdl, **kw)
 
     def pseudo_validate(self, validation_std_beta=None, validation_ld=None):
         """Pseudo-R^2 ``(r'b)^2 / (b'Rb)`` of every model against standardised marginal betas of an independent cohort
@@ -142,7 +98,7 @@ class ClumpThreshold:
             return _pseudo_r2_external(validation_ld, vb, self.post_mean_beta, device=getattr(self, "device", 0))
         chroms = self.chromosomes
         r = np.concatenate([np.asarray(vb[c], dtype=np.float64) for c in chroms])
-        beta = np.concatenate([self.post_mean_beta[c] for c in chroms], axis=0)
+        beta = self._concat(self.post_mean_beta)
         if self._plan is not None:
             return pseudo_r2(self._plan, r, beta, dq_scale=self.dequantize_scale)
         lb, ip, data = self._ld                                # (host path: R b in float64 from the arrays)

@@ -19,11 +19,10 @@ import warnings
 
 import numpy as np
 
-from ..data import merge_ld_arrays
-from ._ld_loading import LoadedLD, ld_form, load_ld_in_order, open_plan
+from ._merged_plan import MergedPlanModel
 
 
-class LDPredInf:
+class LDPredInf(MergedPlanModel):
 
     def __init__(self, gdl, h2=None, float_precision="float32", low_memory=True, dequantize_on_the_fly=False,
                  device=None, solve_fn=None, comm=None, score_fn=None):
@@ -42,75 +41,27 @@ class LDPredInf:
         :param score_fn: test hook -- a callable with `viprs_amd.stats.ldsc.ld_scores_host`'s signature that computes the
             LD scores of ``h2=None`` (the default on the host path: `ld_scores_host` itself).
         """
-        if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
-            raise AssertionError("The data loader must contain summary statistics and LD matrices.")
-        if comm is not None and comm.world_size > 1:
-            raise NotImplementedError("LDPredInf runs on one rank only (world_size > 1: the solve is not sharded)")
-        self.gdl = gdl
+        self._set_loader(gdl, comm, not_sharded="solve")
         self.h2 = h2
-        self.float_precision = float_precision
-        self._T = np.dtype(float_precision)
-        self.low_memory = bool(low_memory)
         self._solve_fn = solve_fn
-        self.shapes = {c: int(s) for c, s in gdl.shapes.items()}
         self._sample_size = max(float(np.max(s.n_per_snp)) for s in gdl.sumstats_table.values())
-
-        ld_mats = gdl.get_ld_matrices()
-        chroms = self.chromosomes
-        corr = None
+        lb, ip, data, corr = self._load(float_precision, low_memory, dequantize_on_the_fly, device, solve_fn is not None,
+                                        "LDPredInf needs a HIP device: the solve has no CPU fallback", ld_correction=h2 is None)
         if h2 is None:
-            from ..stats.ldsc import ld_correction
-            try:
-                corr = np.concatenate([ld_correction(ld_mats[c], self.shapes[c], where=f"chromosome {c}") for c in chroms])
-            except ValueError as e:
-                raise ValueError("LDPredInf(h2=None) estimates h2 by LD-score regression (the reference's default, "
-                                 f"magenpy.stats.h2.ldsc.simple_ldsc) -- {e}  Or pass h2.") from e
-        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
-            ld_mats, chroms, self.low_memory, dequantize_on_the_fly, float_precision, expand_ld_on_device=False)
-        self.std_beta = {c: np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T) for c in chroms}
-        # one plan over the concatenated chromosomes (LD blocks never span chromosomes)
-        lb, ip, data, self._seg = merge_ld_arrays(
-            chroms, self.shapes, {c: ld.left_bound for c, ld in loaded.items()}, {c: ld.indptr for c, ld in loaded.items()},
-            {c: ld.data for c, ld in loaded.items()})
-        del loaded
-        self._plan = None
-        if solve_fn is None:
-            from .. import _lib
-            if _lib.device_count() < 1:
-                raise RuntimeError("LDPredInf needs a HIP device: the solve has no CPU fallback")
-            self.device = int(device) if device is not None else 0
-            self._plan = open_plan(LoadedLD(lb, ip, data, ld_form(self.low_memory)), self.device)
-        else:
-            self._ld = (lb, ip, data)
-        if h2 is None:
-            self.h2 = self._estimate_h2(lb, ip, data, corr, score_fn)
+            self.h2 = self._ldsc_h2(lb, ip, data, corr, score_fn)
+            if not 0.0 < self.h2 <= 1.0:
+                raise ValueError(f"LDPredInf(h2=None): the LD-score regression estimate h2 = {self.h2!r} is not in (0, 1]; "
+                                 "pass h2")
         self.lam = None
         self.post_mean_beta = None
         self.solve_info = None
 
-    def _estimate_h2(self, lb, ip, data, corr, score_fn):
-        """`simple_ldsc` over the model's own LD: corrected unit-weight scores of its plan (the host path: `score_fn` or
-        `ld_scores_host`), then the estimate over all chromosomes."""
-        from ..stats.ldsc import ld_scores_host, ldsc_estimate_over
-        if self._plan is not None and score_fn is None:
-            scores = self._plan.ld_scores(None, corr, dq_scale=self.dequantize_scale, float_precision=self.float_precision)
-        else:
-            scores = (score_fn or ld_scores_host)(lb, ip, data, self.low_memory, None, corr, self.dequantize_scale)
-        self.ld_score = {c: np.asarray(scores[a:e], dtype=np.float64) for c, (a, e) in self._seg.items()}
-        h2 = ldsc_estimate_over(self.gdl.sumstats_table, self.ld_score, self.chromosomes)
-        if not 0.0 < h2 <= 1.0:
-            raise ValueError(f"LDPredInf(h2=None): the LD-score regression estimate h2 = {h2!r} is not in (0, 1]; pass h2")
-        return h2
-
-    @property
-    def chromosomes(self):
-        return sorted(self.shapes)
-
-    @property
-    def m(self):
-        return int(self.gdl.m)
-
-    n_snps = m
+    def _ld_correction(self, ld_mats):
+        try:
+            return super()._ld_correction(ld_mats)
+        except ValueError as e:
+            raise ValueError("LDPredInf(h2=None) estimates h2 by LD-score regression (the reference's default, "
+                             f"magenpy.stats.h2.ldsc.simple_ldsc) -- {e}  Or pass h2.") from e
 
     @property
     def n(self):
@@ -118,15 +69,6 @@ class LDPredInf:
 
     def get_heritability(self):
         return self.h2
-
-    def get_posterior_mean_beta(self):
-        return self.post_mean_beta
-
-    def predict(self, test_gdl=None, **kw):
-        """Polygenic scores of the training loader's genotyped samples, or of `test_gdl`'s (BayesPRSModel.py:229-250):
-        `viprs_amd.genotypes.model_predict`."""
-        from ..genotypes import model_predict
-        return model_predict(self, test_gdl, **kw)
 
     def fit(self, solver="minres", rtol=None, maxiter=None, x0=None, **solver_kwargs):
         """Solves ``(R + lam I) beta = beta_hat`` with ``lam = M / (N h2)`` (LDPredInf.py:81-86) for the standardised
@@ -141,7 +83,7 @@ class LDPredInf:
             raise ValueError(f"unknown solver {solver!r}: 'minres'")
         chroms = self.chromosomes
         self.lam = self.n_snps / (self.n * self.h2)
-        b = np.concatenate([self.std_beta[c] for c in chroms])
+        b = self._concat(self.std_beta)
         if isinstance(x0, dict):
             x0 = np.concatenate([np.asarray(x0[c]) for c in chroms])
         if x0 is not None:
@@ -153,7 +95,7 @@ class LDPredInf:
             x, info = self._plan.solve_ridge(b, self.lam, dq_scale=self.dequantize_scale, rtol=rtol, maxiter=maxiter,
                                              x0=x0)
         self.solve_info = info
-        self.post_mean_beta = {c: np.array(x[a:e]) for c, (a, e) in self._seg.items()}
+        self.post_mean_beta = self._split(x)
         if not info.converged:
             warnings.warn("Maximum iterations reached without convergence.\n"
                           "You may need to run the model for more iterations.", RuntimeWarning, stacklevel=2)

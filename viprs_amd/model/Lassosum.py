@@ -17,8 +17,7 @@ tests drive the host logic with `viprs_amd.stats.enet.enet_sweep_host`; without 
 """
 import numpy as np
 
-from ..data import merge_ld_arrays
-from ._ld_loading import LoadedLD, ld_form, load_ld_in_order, open_plan
+from ._chain_engines import DeviceColumns, HostColumns
 from .ClumpThreshold import ClumpThreshold
 
 
@@ -41,10 +40,15 @@ class Lassosum(ClumpThreshold):
         :param sweep_fn: test hook -- a callable with `viprs_amd.stats.enet.enet_sweep_host`'s signature that replaces the
             device sweep (called once per column and sweep).
         """
-        if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
-            raise AssertionError("The data loader must contain summary statistics and LD matrices.")
-        if comm is not None and comm.world_size > 1:
-            raise NotImplementedError("Lassosum runs on one rank only (world_size > 1: the sweep is not sharded)")
+        self._set_loader(gdl, comm)
+        self._configure(s, lambdas, tol, max_sweeps, float_precision, sweep_fn)
+        self._set_penalty(penalty_factor)
+        self._load("float32", low_memory, dequantize_on_the_fly, device, sweep_fn is not None,
+                   "Lassosum needs a HIP device (viprs_amd.stats.enet.enet_sweep_host is the sweep on the host: "
+                   "pass it as sweep_fn)")
+
+    def _configure(self, s, lambdas, tol, max_sweeps, float_precision, sweep_fn):
+        """What a fit needs beside the data and the penalty factors: checked and stored by both constructors."""
         if np.dtype(float_precision) != np.float32:
             raise ValueError("Lassosum: float_precision must be 'float32' (the elastic-net sweep has no float64 form)")
         self.s = np.atleast_1d(np.asarray(s, dtype=np.float64))
@@ -60,48 +64,37 @@ class Lassosum(ClumpThreshold):
         if not (tol >= 0) or int(max_sweeps) < 1:
             raise ValueError("tol >= 0 and max_sweeps >= 1")
         self.tol, self.max_sweeps = float(tol), int(max_sweeps)
-        self.gdl = gdl
-        self.float_precision = "float32"
-        self._T = np.dtype(np.float32)
-        self.low_memory = bool(low_memory)
         self._sweep_fn = sweep_fn
-        self.shapes = {c: int(n) for c, n in gdl.shapes.items()}
-        chroms = self.chromosomes
-        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
-            gdl.get_ld_matrices(), chroms, self.low_memory, dequantize_on_the_fly, float_precision, expand_ld_on_device=False)
-        self.std_beta = {c: np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T) for c in chroms}
-        if penalty_factor is None:
-            w = np.ones(self.m)
-        elif isinstance(penalty_factor, dict):
-            w = np.concatenate([np.asarray(penalty_factor[c], dtype=np.float64) for c in chroms])
-        else:
-            w = np.asarray(penalty_factor, dtype=np.float64)
-        if w.shape != (self.m,) or not np.all(np.isfinite(w)) or np.any(w < 0):
-            raise ValueError("penalty_factor: one finite value >= 0 per SNP")
-        self.penalty_factor = w
-        # one plan over the concatenated chromosomes (LD blocks never span chromosomes)
-        lb, ip, data, self._seg = merge_ld_arrays(
-            chroms, self.shapes, {c: ld.left_bound for c, ld in loaded.items()}, {c: ld.indptr for c, ld in loaded.items()},
-            {c: ld.data for c, ld in loaded.items()})
-        del loaded
-        self._plan = None
-        self._ld = (lb, ip, data)                               # (the host path of the sweep and of `pseudo_validate`)
-        if sweep_fn is None:
-            from .. import _lib
-            if _lib.device_count() < 1:
-                raise RuntimeError("Lassosum needs a HIP device (viprs_amd.stats.enet.enet_sweep_host is the sweep on the host: "
-                                   "pass it as sweep_fn)")
-            self.device = int(device) if device is not None else 0
-            self._plan = open_plan(LoadedLD(lb, ip, data, ld_form(self.low_memory)), self.device)
-            self._ld = None
         self.n_models = int(self.s.shape[0] * self.lambdas.shape[0])
         self.post_mean_beta = None
         self.grid_table = None
         self.validation_result = None
         self.best_model_idx = None
 
+    def _set_penalty(self, penalty_factor):
+        if penalty_factor is None:
+            w = np.ones(self.m)
+        elif isinstance(penalty_factor, dict):
+            w = np.concatenate([np.asarray(penalty_factor[c], dtype=np.float64) for c in self.chromosomes])
+        else:
+            w = np.asarray(penalty_factor, dtype=np.float64)
+        if w.shape != (self.m,) or not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("penalty_factor: one finite value >= 0 per SNP")
+        self.penalty_factor = w
+
+    @classmethod
+    def from_plan(cls, plan, std_beta, dq_scale, s=(0.2, 0.5, 0.9, 1.0), lambdas=None, penalty_factor=None, tol=1e-4,
+                  max_sweeps=1000):
+        """A model on an existing `LDPlan` (`MergedPlanModel._attach`: one chromosome, the LD may exist on the device only).
+        Device sweep only; the plan stays the caller's."""
+        self = cls.__new__(cls)
+        self._configure(s, lambdas, tol, max_sweeps, "float32", None)
+        self._attach(plan, dq_scale, std_beta)
+        self._set_penalty(penalty_factor)
+        return self
+
     # -- the two engines of the path: a grid state on the device, or arrays swept by the hook -------------------------------
-    class _Device:
+    class _Device(DeviceColumns):
         def __init__(self, plan, beta, mult, dq):
             from ..plan import DeviceState
             self.dq = dq
@@ -122,16 +115,7 @@ class Lassosum(ClumpThreshold):
         def eta(self):
             return self.st.download("eta")
 
-        def zero_column(self, g):
-            for k in ("eta", "q"):
-                a = self.st.download(k)
-                a[:, g] = 0
-                self.st.upload(k, a)
-
-        def close(self):
-            self.st.close()
-
-    class _Host:
+    class _Host(HostColumns):
         def __init__(self, fn, ld, low_memory, beta, mult, dq):
             self.fn, self.ld, self.low_memory, self.beta, self.mult, self.dq = fn, ld, low_memory, beta, mult, dq
             self._eta, self.q, self.ed = (np.zeros(mult.shape, dtype=np.float32, order="F") for _ in range(3))
@@ -151,20 +135,13 @@ class Lassosum(ClumpThreshold):
         def eta(self):
             return self._eta.copy()
 
-        def zero_column(self, g):
-            self._eta[:, g] = 0
-            self.q[:, g] = 0
-
-        def close(self):
-            pass
-
     def fit(self):
         """The path over `lambdas` (descending, warm starts) for every `s`; model ``i_s * n_lambda + k``."""
         import pandas as pd
         from ..stats.enet import enet_objective
         f32 = np.float32
         m, n_lam = self.m, self.lambdas.shape[0]
-        beta_hat = np.concatenate([self.std_beta[c] for c in self.chromosomes])
+        beta_hat = self._concat(self.std_beta)
         path_s = [i for i, v in enumerate(self.s) if v < 1.0]                 # column g of the state: s[path_s[g]]
         G = len(path_s)
         beta = np.zeros((m, self.n_models), dtype=f32)
@@ -218,7 +195,7 @@ class Lassosum(ClumpThreshold):
                             r.update(n_nonzero=int(last[g][5]), objective=float(enet_objective(last[g], s_eff[g])))
             finally:
                 eng.close()
-        self.post_mean_beta = {c: np.array(beta[a:e]) for c, (a, e) in self._seg.items()}
+        self.post_mean_beta = self._split(beta)
         self.grid_table = pd.DataFrame(rows, columns=["s", "lambda", "n_sweeps", "converged", "diverged", "n_nonzero",
                                                       "objective"])
         self.validation_result = self.grid_table.copy()

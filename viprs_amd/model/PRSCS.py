@@ -26,8 +26,7 @@ finite or exceeds ``sum beta_hat^2`` is ``diverged``: zero from there on, and ou
 """
 import numpy as np
 
-from ..data import merge_ld_arrays
-from ._ld_loading import LoadedLD, ld_form, load_ld_in_order, open_plan
+from ._chain_engines import DeviceChains, HostChains, divergence_rule, tail_mean
 from .ClumpThreshold import ClumpThreshold
 
 
@@ -52,10 +51,7 @@ class PRSCS(ClumpThreshold):
         :param keep_draws_log: device path -- `draws_log[k]` keeps the ``(U, noise)`` of sweep k and `variates_log[k]` the
             ``(ub, z1, z2, e)`` of update k, ``(m, G)`` each (tests).
         """
-        if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
-            raise AssertionError("The data loader must contain summary statistics and LD matrices.")
-        if comm is not None and comm.world_size > 1:
-            raise NotImplementedError("PRSCS runs on one rank only (world_size > 1: the sweep is not sharded)")
+        self._set_loader(gdl, comm)
         if float(a) != 1.0 or float(b) != 0.5:
             raise NotImplementedError("PRSCS: only a = 1, b = 0.5 (the closed-form draws of delta and psi need them)")
         if np.dtype(float_precision) != np.float32:
@@ -75,92 +71,39 @@ class PRSCS(ClumpThreshold):
             raise ValueError("phi: positive numbers or None")
         self.n_models = len(self.phi)
         self.seed = int(seed)
-        self.gdl = gdl
-        self.float_precision = "float32"
-        self._T = np.dtype(np.float32)
-        self.low_memory = bool(low_memory)
         self._sweep_fn, self._draws_fn, self._variates_fn = sweep_fn, draws_fn, variates_fn
         self._keep_draws_log = bool(keep_draws_log)
         self.draws_log, self.variates_log = [], []
-        self.shapes = {c: int(n) for c, n in gdl.shapes.items()}
-        chroms = self.chromosomes
-        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
-            gdl.get_ld_matrices(), chroms, self.low_memory, dequantize_on_the_fly, float_precision, expand_ld_on_device=False)
-        self.std_beta = {c: np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T) for c in chroms}
-        self._n_per_snp = np.concatenate([np.asarray(gdl.sumstats_table[c].n_per_snp, dtype=np.float64).ravel() for c in chroms])
-        # one plan over the concatenated chromosomes (LD blocks never span chromosomes)
-        lb, ip, data, self._seg = merge_ld_arrays(
-            chroms, self.shapes, {c: ld.left_bound for c, ld in loaded.items()}, {c: ld.indptr for c, ld in loaded.items()},
-            {c: ld.data for c, ld in loaded.items()})
-        del loaded
-        self._plan = None
-        self._ld = (lb, ip, data)                               # (the host path of the sweep and of `pseudo_validate`)
-        if sweep_fn is None:
-            from .. import _lib
-            if _lib.device_count() < 1:
-                raise RuntimeError("PRSCS needs a HIP device (viprs_amd.stats.gibbs.gibbs_sweep_host is the sweep on the host: "
-                                   "pass it as sweep_fn)")
-            self.device = int(device) if device is not None else 0
-            self._plan = open_plan(LoadedLD(lb, ip, data, ld_form(self.low_memory)), self.device)
-            self._ld = None
+        self._load("float32", low_memory, dequantize_on_the_fly, device, sweep_fn is not None,
+                   "PRSCS needs a HIP device (viprs_amd.stats.gibbs.gibbs_sweep_host is the sweep on the host: "
+                   "pass it as sweep_fn)",
+                   n_per_snp=True)
         self.post_mean_beta = None
         self.grid_table = None
         self.validation_result = None
         self.best_model_idx = None
         self.phi_est = self.sigma2_est = self.phi_history = self.sigma2_history = None
 
-    # -- the two engines of a fit: a grid state on the device, or arrays on the host ------------------------------------------
-    class _Device:
-        def __init__(self, model, beta, G):
-            from ..plan import DeviceState
-            self.model, self.dq = model, model.dequantize_scale
-            self.st = DeviceState(model._plan, "float32", model="grid", width=G, placement="off")
-            self.st.upload("std_beta", beta)
-            self.st.set_n_per_snp(model._n_per_snp)
-            self.st.gibbs_reset_mean()
-
+    # -- the two engines of a fit (`_chain_engines`): what PRS-CS adds is the update of the scales between two sweeps ---------
+    class _Device(DeviceChains):
         def prepare(self, params):
             self.st.cs_update(params, self.model.psi_max, prepare_only=True, sync=False)
 
-        def sweep(self, active, draw_index):
-            self.st.gibbs_sweep(self.dq, active_model_idx=active, seed=self.model.seed, draw_index=draw_index, sync=False)
-            sums = self.st.enet_sums(active), self.st.cs_sums(active)
-            if self.model._keep_draws_log:
-                self.model.draws_log.append((self.st.gibbs_download("unif"), self.st.gibbs_download("noise")))
-            return sums
+        def sums(self, active):
+            return self.st.enet_sums(active), self.st.cs_sums(active)
 
         def update(self, params, draw_index):
             self.st.cs_update(params, self.model.psi_max, seed=self.model.seed, draw_index=draw_index, sync=False)
             if self.model._keep_draws_log:
                 self.model.variates_log.append(tuple(self.st.cs_download(k) for k in ("ub", "z1", "z2", "e")))
 
-        def accumulate(self, active):
-            self.st.gibbs_accumulate(active)
-
-        def mean_sum(self):
-            return self.st.gibbs_download("mean_sum")
-
-        def zero_column(self, g):
-            for k in ("eta", "q"):
-                a = self.st.download(k)
-                a[:, g] = 0
-                self.st.upload(k, a)
-
-        def close(self):
-            self.st.close()
-
-    class _Host:
+    class _Host(HostChains):
         def __init__(self, model, beta, G):
             from ..stats.cs import cs_variates_host
-            from ..stats.gibbs import gibbs_draws_host
-            self.model, self.beta, self.dq = model, beta, model.dequantize_scale
-            self.draws = model._draws_fn or gibbs_draws_host
+            super().__init__(model, beta, G)
             self.variates = model._variates_fn or cs_variates_host
-            shape = (model.m, G)
-            self.mm, self.hvt, self.ulog, self._eta, self.q, self.ed, self.mu, self.gam, self.delta = (
-                np.zeros(shape, dtype=np.float32, order="F") for _ in range(9))
-            self.psi = np.ones(shape, dtype=np.float32, order="F")
-            self.mean = np.zeros(shape, dtype=np.float64, order="F")
+            self.delta = np.zeros((model.m, G), dtype=np.float32, order="F")
+            self.psi = np.ones((model.m, G), dtype=np.float32, order="F")
 
         def _update(self, params, variates, prepare_only):
             from ..stats.cs import cs_update_host
@@ -170,20 +113,9 @@ class PRSCS(ClumpThreshold):
         def prepare(self, params):
             self._update(params, None, True)
 
-        def sweep(self, active, draw_index):
+        def sums(self, active):
             from ..stats.cs import cs_sums_host
-            from ..stats.enet import enet_sums_host
-            lb, ip, data = self.model._ld
-            a = np.asarray(active)
-            unif, noise = self.draws(self.model.seed, draw_index, self.hvt, a)
-            pick = lambda x: np.asfortranarray(x[:, a])
-            eta, q = pick(self._eta), pick(self.q)
-            res = self.model._sweep_fn(lb, ip, data, self.model.low_memory, self.beta, pick(self.mm), pick(self.hvt),
-                                       pick(self.ulog), pick(unif), pick(noise), eta, q, self.dq)
-            for dst, src in zip((self.ed, self.mu, self.gam, self._eta, self.q), tuple(res) + (eta, q)):
-                dst[:, a] = src
-            return (enet_sums_host(self.beta, self.hvt, self._eta, self.q, self.ed, cols=active, grid=True),
-                    cs_sums_host(self.model._n_per_snp, self._eta, self.psi, self.delta, cols=active))
+            return super().sums(active), cs_sums_host(self.model._n_per_snp, self._eta, self.psi, self.delta, cols=active)
 
         def update(self, params, draw_index):
             cols = np.asarray(params)[:, 0].astype(np.int64)
@@ -193,28 +125,13 @@ class PRSCS(ClumpThreshold):
                 dst[:, cols] = src[:, cols] if src.shape == dst.shape else src      # (m, G) from a log, or (m, len(cols))
             self._update(params, full, False)
 
-        def accumulate(self, active):
-            for g in active:
-                self.mean[:, g] += self.gam[:, g].astype(np.float64) * self.mu[:, g].astype(np.float64)
-
-        def mean_sum(self):
-            return self.mean.copy()
-
-        def zero_column(self, g):
-            self._eta[:, g] = 0
-            self.q[:, g] = 0
-
-        def close(self):
-            pass
-
     def fit(self):
         """The chains in lock step: `n_iter` iterations of (sweep, sums, the two scalar draws, update); after `n_burnin`
         every `thin`-th iteration adds its conditional means to the posterior mean."""
         import pandas as pd
         from ..stats.cs import cs_phi_draw, cs_sigma2_draw
         m = self.m
-        beta_hat = np.concatenate([self.std_beta[c] for c in self.chromosomes])
-        limit = float(beta_hat.astype(np.float64) @ beta_hat.astype(np.float64))
+        beta_hat, diverges = divergence_rule(self)
         nbar = float(np.mean(self._n_per_snp))
         G = self.n_models
         auto = np.array([v is None for v in self.phi])
@@ -237,7 +154,7 @@ class PRSCS(ClumpThreshold):
                 enet, cs = eng.sweep(active, it)
                 still = []
                 for g, row, c in zip(active, enet, cs):
-                    if not np.isfinite(row[3]) or row[3] > limit:
+                    if diverges(row[3]):
                         diverged[g] = True
                         eng.zero_column(int(g))
                         continue
@@ -261,18 +178,15 @@ class PRSCS(ClumpThreshold):
         mean[:, diverged] = 0.0
         beta = mean.astype(np.float32)
         self.phi_history, self.sigma2_history = phi_hist, s2_hist
-        import warnings
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", RuntimeWarning)
-            self.phi_est = np.where(diverged, np.nan, np.nanmean(phi_hist[self.n_burnin:], axis=0))
-            self.sigma2_est = np.where(diverged, np.nan, np.nanmean(s2_hist[self.n_burnin:], axis=0))
+        self.phi_est = tail_mean(phi_hist, self.n_burnin, diverged)
+        self.sigma2_est = tail_mean(s2_hist, self.n_burnin, diverged)
         self.grid_table = pd.DataFrame(dict(phi=[np.nan if v is None else v for v in self.phi], auto=auto, phi_est=self.phi_est,
                                             sigma2_est=self.sigma2_est, diverged=diverged))
         self.validation_result = self.grid_table.copy()
         if G == 1:
-            self.post_mean_beta = {c: np.array(beta[a:e, 0]) for c, (a, e) in self._seg.items()}
+            self.post_mean_beta = self._split(beta[:, 0])
             self.best_model_idx = 0                                 # one model: nothing to select
         else:
-            self.post_mean_beta = {c: np.array(beta[a:e]) for c, (a, e) in self._seg.items()}
+            self.post_mean_beta = self._split(beta)
             self.best_model_idx = None
         return self

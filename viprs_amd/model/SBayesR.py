@@ -37,11 +37,9 @@ reference has no such class.
 """
 import numpy as np
 
-from ..data import merge_ld_arrays
 from ..stats import bayesr as B
-from ._ld_loading import LoadedLD, ld_form, load_ld_in_order, open_plan
+from ._chain_engines import divergence_rule, tail_mean
 from .ClumpThreshold import ClumpThreshold
-from .LDpred2 import LDpred2
 
 
 class SBayesR(ClumpThreshold):
@@ -62,50 +60,25 @@ class SBayesR(ClumpThreshold):
         :param score_fn: as in `LDPredInf`: the LD scores of ``h2_init='ldsc'``.
         :param keep_draws_log: device backend -- `draws_log[draw_index]` keeps the ``(U, z)`` that sweep used (tests).
         """
-        if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
-            raise AssertionError("The data loader must contain summary statistics and LD matrices.")
-        if comm is not None and comm.world_size > 1:
-            raise NotImplementedError("SBayesR runs on one rank only (world_size > 1: the sweep is not sharded)")
-        self._configure(gamma, pi, n_iter, n_burnin, thin, n_chains, seed, float_precision, low_memory, backend, sweep_fn,
-                        draws_fn, keep_draws_log)
-        host = self._sweep_fn is not None
-        self.gdl = gdl
-        self.shapes = {c: int(n) for c, n in gdl.shapes.items()}
-        chroms = self.chromosomes
-        ld_mats = gdl.get_ld_matrices()
-        corr = None
-        if isinstance(h2_init, str):
-            if h2_init != "ldsc":
-                raise ValueError(f"h2_init: 'ldsc' or a number, got {h2_init!r}")
-            from ..stats.ldsc import ld_correction
-            corr = np.concatenate([ld_correction(ld_mats[c], self.shapes[c], where=f"chromosome {c}") for c in chroms])
-        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
-            ld_mats, chroms, self.low_memory, dequantize_on_the_fly, float_precision, expand_ld_on_device=False)
-        self.std_beta = {c: np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr()).astype(self._T) for c in chroms}
-        self._n_per_snp = np.concatenate([np.asarray(gdl.sumstats_table[c].n_per_snp, dtype=np.float64).ravel() for c in chroms])
-        # one plan over the concatenated chromosomes (LD blocks never span chromosomes)
-        lb, ip, data, self._seg = merge_ld_arrays(
-            chroms, self.shapes, {c: ld.left_bound for c, ld in loaded.items()}, {c: ld.indptr for c, ld in loaded.items()},
-            {c: ld.data for c, ld in loaded.items()})
-        del loaded
-        self._plan = None
-        self._ld = (lb, ip, data)                               # (the host backend and the host path of `pseudo_validate`)
-        if not host:
-            from .. import _lib
-            if _lib.device_count() < 1:
-                raise RuntimeError("SBayesR needs a HIP device (backend='host' runs viprs_amd.stats.bayesr on the CPU)")
-            self.device = int(device) if device is not None else 0
-            self._plan = open_plan(LoadedLD(lb, ip, data, ld_form(self.low_memory)), self.device)
-        self.h2_init = self._ldsc_h2(lb, ip, data, corr, score_fn) if isinstance(h2_init, str) else float(h2_init)
+        self._set_loader(gdl, comm)
+        self._configure(gamma, pi, n_iter, n_burnin, thin, n_chains, seed, float_precision, backend, sweep_fn, draws_fn,
+                        keep_draws_log)
+        ldsc = isinstance(h2_init, str)
+        if ldsc and h2_init != "ldsc":
+            raise ValueError(f"h2_init: 'ldsc' or a number, got {h2_init!r}")
+        lb, ip, data, corr = self._load(
+            "float32", low_memory, dequantize_on_the_fly, device, self._sweep_fn is not None,
+            "SBayesR needs a HIP device (backend='host' runs viprs_amd.stats.bayesr on the CPU)", ld_correction=ldsc,
+            n_per_snp=True)
+        self._set_h2_init(self._ldsc_h2(lb, ip, data, corr, score_fn) if ldsc else h2_init)
+
+    def _set_h2_init(self, h2_init):
+        self.h2_init = float(h2_init)
         if not self.h2_init > 0.0:
             raise ValueError(f"h2_init = {self.h2_init!r}: a positive heritability is needed")
-        if self._plan is not None:
-            self._ld = None
 
-    _ldsc_h2 = LDpred2._ldsc_h2
-
-    def _configure(self, gamma, pi, n_iter, n_burnin, thin, n_chains, seed, float_precision, low_memory, backend, sweep_fn,
-                   draws_fn, keep_draws_log):
+    def _configure(self, gamma, pi, n_iter, n_burnin, thin, n_chains, seed, float_precision, backend, sweep_fn, draws_fn,
+                   keep_draws_log):
         """What a fit needs beside the data: checked and stored by both constructors."""
         if np.dtype(float_precision) != np.float32:
             raise ValueError("SBayesR: float_precision must be 'float32' (the sweep has no float64 form)")
@@ -124,9 +97,6 @@ class SBayesR(ClumpThreshold):
             raise ValueError(f"backend: 'device' or 'host', got {backend!r}")
         host = backend == "host" or sweep_fn is not None
         self.seed = int(seed)
-        self.float_precision = "float32"
-        self._T = np.dtype(np.float32)
-        self.low_memory = bool(low_memory)
         self._sweep_fn = (sweep_fn or B.bayesr_sweep_host) if host else None
         self._draws_fn = draws_fn or B.bayesr_draws_host
         self._keep_draws_log = bool(keep_draws_log)
@@ -141,26 +111,14 @@ class SBayesR(ClumpThreshold):
     @classmethod
     def from_plan(cls, plan, std_beta, n_per_snp, dq_scale, h2_init, gamma=B.DEFAULT_GAMMA, pi=B.DEFAULT_PI, n_iter=1000,
                   n_burnin=250, thin=1, n_chains=1, seed=0, keep_draws_log=False):
-        """A model on an existing `LDPlan` (one chromosome; the LD may exist on the device only: synthetic plans, plans another
-        model has built): `std_beta` float32 ``(m,)``, `n_per_snp` ``(m,)``, `dq_scale` the plan's de-quantisation scale,
-        `h2_init` a number.  Device backend only; the plan stays the caller's."""
-        from .. import _lib
+        """A model on an existing `LDPlan` (`MergedPlanModel._attach`: one chromosome; the LD may exist on the device only:
+        synthetic plans, plans another model has built); `h2_init` a number.  Device backend only; the plan stays the
+        caller's."""
         self = cls.__new__(cls)
-        self._configure(gamma, pi, n_iter, n_burnin, thin, n_chains, seed, "float32", bool(plan.info(_lib.INFO_LOW_MEMORY)), "device", None, None,
-                        keep_draws_log)
-        m = int(plan.m)
-        std_beta = np.ascontiguousarray(std_beta, dtype=np.float32)
-        if std_beta.shape != (m,) or np.shape(n_per_snp) != (m,):
-            raise ValueError(f"std_beta, n_per_snp: arrays of shape ({m},)")
-        if not float(h2_init) > 0.0:
-            raise ValueError(f"h2_init = {h2_init!r}: a positive heritability is needed")
-        self.gdl = type("PlanLoader", (), {"m": m, "shapes": {1: m}})
-        self.shapes, self._seg = {1: m}, {1: (0, m)}
-        self.std_beta, self._n_per_snp = {1: std_beta}, np.asarray(n_per_snp, dtype=np.float64)
-        self._plan, self._ld, self.device = plan, None, int(plan.info(_lib.INFO_DEVICE))
-        self.dequantize_on_the_fly, self.dequantize_scale, self.h2_init = True, float(dq_scale), float(h2_init)
+        self._configure(gamma, pi, n_iter, n_burnin, thin, n_chains, seed, "float32", "device", None, None, keep_draws_log)
+        self._attach(plan, dq_scale, std_beta, n_per_snp)
+        self._set_h2_init(h2_init)
         return self
-
 
     # -- the two backends of a chain: a mixture state on the device, or arrays swept on the host --------------------------------
     class _Device:
@@ -219,7 +177,7 @@ class SBayesR(ClumpThreshold):
         def close(self):
             pass
 
-    def _run_chain(self, chain, beta_hat, limit):
+    def _run_chain(self, chain, beta_hat, diverges):
         """One chain: ``(mean_sum, pip_sum, n_samples, diverged, histories, sweeps run)``."""
         K, m = self.K, self.m
         rng = np.random.default_rng([self.seed, chain])
@@ -240,7 +198,7 @@ class SBayesR(ClumpThreshold):
                 n_sweeps += 1
                 counts, ssq = s[:K + 1], s[K + 1:2 * K + 1]
                 sum_q_eta, sum_eta2, sum_beta_eta = s[2 * K + 1:2 * K + 4]
-                if not np.isfinite(sum_eta2) or sum_eta2 > limit:
+                if diverges(sum_eta2):
                     diverged = True
                     break
                 if it >= self.n_burnin and (it - self.n_burnin) % self.thin == 0:
@@ -262,8 +220,7 @@ class SBayesR(ClumpThreshold):
         """The chains one after the other: `n_burnin` sweeps, then the sweeps whose Rao-Blackwellised means are averaged."""
         import pandas as pd
         m = self.m
-        beta_hat = np.concatenate([self.std_beta[c] for c in self.chromosomes])
-        limit = float(beta_hat.astype(np.float64) @ beta_hat.astype(np.float64))
+        beta_hat, diverges = divergence_rule(self)
         C = self.n_chains
         self.draws_log = {}
         means, pips = np.zeros((m, C)), np.zeros((m, C))
@@ -271,27 +228,20 @@ class SBayesR(ClumpThreshold):
         self.n_sweeps = np.zeros(C, dtype=np.int64)
         hists = []
         for c in range(C):
-            mean, pip, n, div, hist, self.n_sweeps[c] = self._run_chain(c, beta_hat, limit)
+            mean, pip, n, div, hist, self.n_sweeps[c] = self._run_chain(c, beta_hat, diverges)
             self.diverged[c] = div or n == 0
             if not self.diverged[c]:
                 means[:, c], pips[:, c] = mean / n, pip / n
             hists.append(hist)
         keep = ~self.diverged
-        tail = slice(self.n_burnin, None)
-        with np.errstate(invalid="ignore"):
-            import warnings
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore", RuntimeWarning)
-                est = lambda k: np.array([np.full(h[k].shape[1:], np.nan) if d else np.nanmean(h[k][tail], axis=0)
-                                          for h, d in zip(hists, self.diverged)])
-                self.pi_est, self.sigma2_beta_est, self.sigma2_e_est, self.h2_est = est("pi"), est("sigma2_beta"), est("sigma2_e"), est("h2")
+        est = lambda k: np.array([tail_mean(h[k], self.n_burnin, d) for h, d in zip(hists, self.diverged)])
+        self.pi_est, self.sigma2_beta_est, self.sigma2_e_est, self.h2_est = est("pi"), est("sigma2_beta"), est("sigma2_e"), est("h2")
         self.pi_history = [h["pi"] for h in hists]
         self.h2_history = [h["h2"] for h in hists]
         final = (means[:, keep].mean(axis=1) if keep.any() else np.zeros(m)).astype(np.float32)
         pip = (pips[:, keep].mean(axis=1) if keep.any() else np.zeros(m)).astype(np.float32)
-        self.chain_beta = {c: np.array(means[a:e].astype(np.float32)) for c, (a, e) in self._seg.items()}
-        self.post_mean_beta = {c: np.array(final[a:e]) for c, (a, e) in self._seg.items()}
-        self.pip = {c: np.array(pip[a:e]) for c, (a, e) in self._seg.items()}
+        self.chain_beta = self._split(means.astype(np.float32))
+        self.post_mean_beta, self.pip = self._split(final), self._split(pip)
         self.best_model_idx = 0                                     # one model: nothing to select
         self.grid_table = pd.DataFrame(dict(chain=np.arange(C), diverged=self.diverged, n_sweeps=self.n_sweeps, h2=self.h2_est,
                                             sigma2_beta=self.sigma2_beta_est, sigma2_e=self.sigma2_e_est,

@@ -17,11 +17,10 @@ import warnings
 
 import numpy as np
 
-from ..data import merge_ld_arrays
-from ._ld_loading import LoadedLD, ld_form, load_ld_in_order, open_plan
+from ._merged_plan import MergedPlanModel
 
 
-class SuSiE:
+class SuSiE(MergedPlanModel):
 
     def __init__(self, gdl, L=10, prior_variance=50.0, estimate_prior_variance=True, prior_weights=None,
                  float_precision="float32", low_memory=True, dequantize_on_the_fly=False, device=None, fit_fn=None):
@@ -39,37 +38,18 @@ class SuSiE:
         :param fit_fn: test hook -- a callable with `viprs_amd.stats.susie.susie_host`'s signature that replaces the
             device fit.
         """
-        if gdl.genotype is None and (gdl.ld is None or gdl.sumstats_table is None):
-            raise AssertionError("The data loader must contain summary statistics and LD matrices.")
-        self.gdl = gdl
+        self._set_loader(gdl)
         self.L = int(L)
         self.prior_variance = float(prior_variance)
         self.estimate_prior_variance = bool(estimate_prior_variance)
-        self.float_precision = float_precision
-        self._T = np.dtype(float_precision)
-        self.low_memory = bool(low_memory)
         self._fit_fn = fit_fn
-        self.shapes = {c: int(s) for c, s in gdl.shapes.items()}
-        chroms = self.chromosomes
-        loaded, self.dequantize_on_the_fly, self.dequantize_scale = load_ld_in_order(
-            gdl.get_ld_matrices(), chroms, self.low_memory, dequantize_on_the_fly, float_precision,
-            expand_ld_on_device=False)
-        self._sqrt_n = {c: np.sqrt(np.asarray(gdl.sumstats_table[c].n_per_snp, dtype=np.float64)) for c in chroms}
-        self.z = {c: self._sqrt_n[c] * np.asarray(gdl.sumstats_table[c].get_snp_pseudo_corr(), dtype=np.float64)
-                  for c in chroms}
-        # one plan over the concatenated chromosomes (LD blocks never span chromosomes)
-        lb, ip, data, self._seg = merge_ld_arrays(
-            chroms, self.shapes, {c: ld.left_bound for c, ld in loaded.items()}, {c: ld.indptr for c, ld in loaded.items()},
-            {c: ld.data for c, ld in loaded.items()})
-        del loaded
-        self._ld = (lb, ip, data)                  # (the credible sets' purity and the ELBO read the host arrays)
-        self._plan = None
-        if fit_fn is None:
-            from .. import _lib
-            if _lib.device_count() < 1:
-                raise RuntimeError("SuSiE needs a HIP device: pass fit_fn=viprs_amd.stats.susie.susie_host for a host fit")
-            self.device = int(device) if device is not None else 0
-            self._plan = open_plan(LoadedLD(lb, ip, data, ld_form(self.low_memory)), self.device)
+        # (the credible sets' purity and the ELBO read the host arrays: they are kept beside the plan)
+        self._load(float_precision, low_memory, dequantize_on_the_fly, device, fit_fn is not None,
+                   "SuSiE needs a HIP device: pass fit_fn=viprs_amd.stats.susie.susie_host for a host fit", keep_ld=True,
+                   std_beta=False)
+        table = gdl.sumstats_table
+        self._sqrt_n = {c: np.sqrt(np.asarray(table[c].n_per_snp, dtype=np.float64)) for c in self.chromosomes}
+        self.z = {c: self._sqrt_n[c] * np.asarray(table[c].get_snp_pseudo_corr(), dtype=np.float64) for c in self.chromosomes}
         self.log_prior = self._log_prior(prior_weights)
         self.info = None
         self.post_mean_beta = None
@@ -97,23 +77,9 @@ class SuSiE:
             lp[s:e][on] = np.log(w[s:e][on]) - np.log(tot)
         return lp
 
-    @property
-    def chromosomes(self):
-        return sorted(self.shapes)
-
-    @property
-    def m(self):
-        return int(self.gdl.m)
-
-    n_snps = m
-
-    def _split(self, x):
-        return {c: np.array(x[a:e]) for c, (a, e) in self._seg.items()}
-
     def fit(self, tol=1e-4, max_iter=100):
         """Fits every LD block; a block stops when no `alpha` moved by `tol` in an iteration, or after `max_iter`."""
-        chroms = self.chromosomes
-        z = np.concatenate([self.z[c] for c in chroms])
+        z = self._concat(self.z)
         lb, ip, data = self._ld
         if self._fit_fn is not None:
             info = self._fit_fn(lb, ip, data, self.low_memory, z, self.L, self.prior_variance, self.estimate_prior_variance,
@@ -126,8 +92,7 @@ class SuSiE:
         self.info = info
         self._sets = None
         bbar = np.sum(np.asarray(info.alpha, dtype=np.float64) * np.asarray(info.mu, dtype=np.float64), axis=1)
-        sqrt_n = np.concatenate([self._sqrt_n[c] for c in chroms])
-        self.post_mean_beta = self._split((bbar / sqrt_n).astype(self._T))
+        self.post_mean_beta = self._split((bbar / self._concat(self._sqrt_n)).astype(self._T))
         self.pip = self._split(pips(info))
         if not info.converged:
             warnings.warn("Maximum iterations reached without convergence.\n"
@@ -140,9 +105,6 @@ class SuSiE:
 
     def get_pip(self):
         return self.pip
-
-    def get_posterior_mean_beta(self):
-        return self.post_mean_beta
 
     def credible_sets(self, coverage=0.95, min_abs_corr=0.5, n_purity=100, seed=0):
         """`viprs_amd.stats.susie.credible_sets` of the fit; every set also names its `chromosome` and the SNPs' indices
@@ -163,8 +125,7 @@ class SuSiE:
         from ..stats.susie import susie_elbo
         self._fitted()
         lb, ip, data = self._ld
-        z = np.concatenate([self.z[c] for c in self.chromosomes])
-        return susie_elbo(lb, ip, data, self.low_memory, z, self.info, self.log_prior, self.dequantize_scale)
+        return susie_elbo(lb, ip, data, self.low_memory, self._concat(self.z), self.info, self.log_prior, self.dequantize_scale)
 
     def to_table(self, per_chromosome=False, **cs_kwargs):
         """The fit as a pandas table: CHR, the SNP's index, BETA, PIP and CS -- the number of the credible set
@@ -178,8 +139,3 @@ class SuSiE:
         tables = {c: pd.DataFrame({"CHR": c, "IDX": np.arange(self.shapes[c]), "BETA": self.post_mean_beta[c],
                                    "PIP": self.pip[c], "CS": cs_of[c]}) for c in self.chromosomes}
         return tables if per_chromosome else pd.concat([tables[c] for c in self.chromosomes])
-
-    def predict(self, test_gdl=None, **kw):
-        """Polygenic scores from the posterior mean effects: `viprs_amd.genotypes.model_predict`."""
-        from ..genotypes import model_predict
-        return model_predict(self, test_gdl, **kw)

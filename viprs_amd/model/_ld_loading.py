@@ -17,16 +17,17 @@ Who calls what, and the differences between the entry points -- decisions, each 
 caller                                 ``expand_ld_on_device``    an upper-only store with ``low_memory=False``
 =====================================  =========================  ===========================================================
 `VIPRS.__init__` (`_load_ld`)          None / True / False        None, True: mirrored on the device; False: the ValueError
-`LDPredInf.__init__`                   False                      the matrix's ValueError (never expands)
+`MergedPlanModel._load` (7 models)     False                      the matrix's ValueError (never expands)
 `stats.ldsc.ld_scores`                 None                       scored in the upper form (`LoadedLD.as_stored`)
 `stats.spectrum.ld_spectrum`           None                       mirrored on the device
 `model.VIPRS._pseudo_r2_external`      -- (arrays handed in)      --
 =====================================  =========================  ===========================================================
 
-``dequantize_on_the_fly``: every matrix decides for itself (`LoadedLD.dequantize`).  `VIPRS` and `LDPredInf` thread the
-decision through the chromosomes in sorted order (`load_ld_in_order`) -- the first float-stored chromosome turns it off
-for all later ones -- and take `dequantize_scale` from the FIRST chromosome's matrix; the two `stats` functions decide per
-matrix.  Whether these differences should be unified is not decided here; they are only visible in one place now.
+``dequantize_on_the_fly``: every matrix decides for itself (`LoadedLD.dequantize`).  `VIPRS` and the models on a merged
+plan (`_merged_plan`) thread the decision through the chromosomes in sorted order (`load_ld_in_order`) -- the first
+float-stored chromosome turns it off for all later ones -- and take `dequantize_scale` from the FIRST chromosome's matrix;
+the two `stats` functions decide per matrix.  Whether these differences should be unified is not decided here; they are
+only visible in one place now.
 """
 from collections import namedtuple
 
