@@ -624,6 +624,99 @@ int viprs_state_cs_upload(viprs_state* state, int which, const void* host);
 int viprs_state_cs_download(viprs_state* state, int which, void* host);
 int viprs_plan_last_cs_ms(viprs_plan* plan, double* variates_ms, double* update_ms);
 
+/* ---- PRS-CSx: populations coupled through shared local scales -------------------------------------------------------------------
+ * PRS-CSx (Ruan et al. 2022) fits one PRS-CS chain per population k = 0 .. P - 1, each on its own LD panel and summary
+ * statistics -- here: each a grid state on a plan of its own, swept by viprs_state_gibbs_sweep exactly as in the PRS-CS section
+ * --, and couples them through ONE local scale psi_u per SNP u of the union of the SNP sets: beta_ku ~ N(0, sigma2_k / n_ku *
+ * psi_u), psi_u ~ Gamma(1, delta_u), delta_u ~ Gamma(1/2, phi).  With K_u populations carrying SNP u the conditional is
+ *   psi_u ~ GIG(p = 1 - K_u / 2, 2 delta_u, B_u),  B_u = sum_k n_ku beta_ku^2 / sigma2_k
+ * (density proportional to x^(p - 1) exp(-(a x + b / x) / 2)).  K_u = 1 is the index 1/2 of the PRS-CS section and keeps its
+ * closed form; K_u >= 2 (index 0, -1/2, -1, ...) is drawn by the rejection sampler of Devroye (2014) for the log-concave density
+ * of log X, the algorithm of PRS-CS's gigrnd.  A viprs_csx handle holds the map from union SNPs to the rows of the P states,
+ * the shared psi and delta and the attempt counts; one call per iteration gathers eta from the P states, draws, and scatters
+ * the three sweep inputs back.  The reference has no such model; the definition is this library's own, stated in full.
+ * THE HANDLE.  viprs_csx_create: `states`, n_pop fp32 states of kind VIPRS_MODEL_GRID of one common width G on one device, each
+ * after viprs_state_set_n_per_snp; `row_of`, n_pop x m_union row-major: the row of union SNP u in the plan of population k, or -1.
+ * The handle owns the uploaded map, the shared (m_union, G) float32 psi (1) and delta (0), column-major, the (m_union, G) uint8
+ * attempt counts (0) and a counter of capped draws; it creates the cs buffers of every state (viprs_cs_buffer).  The states
+ * stay the caller's and must outlive the handle.  The kernels run on the stream of population 0's plan.
+ * THE UPDATE.  viprs_csx_update, `params`: n rows (column, phi, sigma2_0 .. sigma2_{P-1}).  Per union SNP u and listed column g, in
+ * float64, every operation separately rounded, no fused multiply-add, products and sums associate from the left:
+ *   1. ub, z1, z2, e: the float32 variates of viprs_state_cs_variates with j = u, counter = (u, g + 2^31, low 32 bits of
+ *      draw_index, high 32 bits of draw_index); psi_old = the shared psi[u, g];
+ *        g15 = 0.5 z2 z2 + e;  delta = g15 / (psi_old + phi);  lam = 2 delta
+ *   2. B = 0; for k ascending over the populations with r = row_of[k][u] >= 0:  B = B + n_kr eta_kr eta_kr / sigma2_k
+ *      (eta_kr = (double)VIPRS_FIELD_ETA[r, g] of state k); K = the number of such populations.
+ *   3. K == 1: with eta, n, sigma2 of the one carrying population, s = |eta| sqrt(n / (lam sigma2)); y = z1 z1;
+ *        A = s + (y + sqrt(y (4 lam s + y))) / (2 lam);  psi = (ub (A + s) <= A) ? A : s s / A
+ *      K >= 2 and B == 0: psi = 2^-40 (the conditional is improper; nothing is drawn, 0 attempts).
+ *      K >= 2 otherwise, with psi(x) = -alpha (cosh(x) - 1) - lambda (exp(x) - x - 1), dpsi(x) = -alpha sinh(x) - lambda (exp(x) - 1)
+ *      and C1 = cosh(1), E1 = exp(1), EM1 = exp(-1) rounded to float64:
+ *        lambda = 0.5 K - 1;  omega = sqrt(lam B);  alpha = sqrt(omega omega + lambda lambda) - lambda
+ *        x = alpha (C1 - 1) + lambda (E1 - 1 - 1);   t = 1 if 0.5 <= x <= 2;  sqrt(2 / (alpha + lambda)) if x > 2;
+ *                                                    log(4 / (alpha + 2 lambda)) if x < 0.5
+ *        x = alpha (C1 - 1) + lambda EM1;            s = 1 if 0.5 <= x <= 2;  sqrt(4 / (alpha C1 + lambda)) if x > 2;  if x < 0.5:
+ *                                                    ia = 1 / alpha;  s = log(1 + ia + sqrt(ia ia + 2 ia));
+ *                                                    and only if lambda > 0:  s = fmin(1 / lambda, s)
+ *        (lambda = 0, two populations, takes the log branch alone: no 1 / lambda is formed)
+ *        eta' = -psi(t);  zeta = -dpsi(t);  theta = -psi(-s);  xi = dpsi(-s);  pe = 1 / xi;  re = 1 / zeta
+ *        td = t - re eta';  sd = s - pe theta;  q = td + sd;  norm = pe + q + re;  cut1 = q / norm;  cut2 = (q + re) / norm
+ *      attempt a = 0, 1, ..: one Philox4x32-10 block, the key of the variates,
+ *        counter = (u, g + 2^31 + (a + 1) 2^16, low 32 bits of draw_index, high 32 bits of draw_index)
+ *      (bits 16..21 of the second word: disjoint from the variates, whose a + 1 is 0, and from the Gibbs draws; hence G < 2^16);
+ *      U, V, W = (double) of the open-unit float32 uniforms (2 (x_i >> 9) + 1) * 2^-24 of its words x0, x1, x2;
+ *        x = -sd + q V if U < cut1;  td - re log(V) if U < cut2;  -sd + pe log(V) otherwise
+ *        gx = exp(-eta' - zeta (x - t)) if x > td;  exp(-theta + xi (x + s)) if x < -sd;  1 otherwise
+ *        accept when W gx <= exp(psi(x))
+ *      THE ATTEMPT CAP IS 32 (VIPRS_CSX_MAX_ATTEMPTS): a draw still rejected at a = 31 keeps that proposal and adds one to the
+ *      handle's counter of capped draws (a global atomic add).  The measured worst rejection share is 0.177 (p = 0, omega = 1):
+ *      0.2^32 is about 4e-23 per draw.  A NaN never accepts: it ends at the cap and stays a NaN.  Then
+ *        lo = lambda / omega;  psi = exp(x) (lo + sqrt(1 + lo lo));  if K > 2 (p < 0): psi = 1 / psi;  psi = psi / sqrt(lam / B)
+ *      The attempt count of (u, g) is a + 1 of the last attempt, 0 where nothing was drawn.  exp, log, cosh, sinh are the device
+ *      library's float64 functions: against a host implementation psi agrees to one float32 ulp, not bit for bit.
+ *   4. psi = psi < 2^-40 ? 2^-40 : psi;  psi = psi > psi_max ? psi_max : psi          (comparisons: a NaN stays a NaN)
+ *      psi32 = (float)psi;  delta32 = (float)delta, stored in the shared psi and delta.
+ *   5. for every carrying population k at its row r: VIPRS_CS_PSI[r, g] = psi32, VIPRS_CS_DELTA[r, g] = delta32, the four
+ *      variates into VIPRS_CS_UB, _Z1, _Z2, _E, and with p = (double)psi32
+ *        mu_mult = (float)(p / (1 + p));  half_var_tau = (float)(n_kr (1 + 1 / p) / (2 sigma2_k));  u_logs = 32.0f
+ *      so that the unchanged viprs_state_cs_sums of state k yields that population's sum eta^2 / psi and sum n eta^2 / psi.
+ * Columns not listed keep their bits, in the handle and in every state.  A handle over one population with the identity map
+ * gives the bits of viprs_state_cs_update, every buffer and field.  Flags, those of viprs_state_cs_update:
+ * VIPRS_CS_KEEP_VARIATES reads ub, z1, z2, e from the cs buffers of the first carrying population instead of drawing them (the
+ * four closed-form variates only: the attempts of the sampler are always drawn); VIPRS_CS_PREPARE_ONLY draws nothing and
+ * rewrites step 5 (psi, delta, the three fields; not the variates) from the stored shared psi and delta.
+ * ORDER ACROSS STREAMS.  The P states sit on P plans with P streams.  The update waits for an event recorded on every member
+ * stream at the call, and every member stream waits for the event recorded behind the update kernel before anything it is
+ * given later: a sweep enqueued before the call is finished before the update reads its eta, a sweep enqueued after the call
+ * reads the new inputs.  Asynchronous unless `sync` != 0.  One grid-stride walk over the n x m_union rectangle, at most 8192
+ * workgroups of 256, no LDS; the rejection loop is per lane.
+ * THE SUMS.  viprs_csx_sums, `out`: n rows of VIPRS_N_CSX_SUMS doubles, one per listed column (`cols` NULL: every column, n = G):
+ *   [0] sum delta   [1] sum psi      over the union, the shared float32 values converted to double,
+ * summed in THE ORDER defined above for the rows of a grid state (cap 256 workgroups).  Synchronous.
+ * REFUSALS of viprs_csx_create, each VIPRS_EINVAL before any allocation: n_pop outside 1..8; a state that is not an fp32
+ * VIPRS_MODEL_GRID state; states of different widths; states on different devices; a state under a (group, column) mask or with
+ * a communicator; a state without viprs_state_set_n_per_snp; a state listed twice; a union row carried by no population; a row
+ * index out of range or listed twice within one population; G >= 2^16; m_union >= 2^32; null pointers.  Of the other calls,
+ * before any launch: a null handle; a column out of range or listed twice; phi or a sigma2 not positive and finite; psi_max
+ * outside (2^-40, inf); an unknown flag; a bad buffer code; null pointers.
+ *   viprs_csx_upload / _download   the shared psi or delta (float32) or the attempt counts (uint8), `which` a viprs_csx_buffer
+ *   viprs_csx_last                 the event time of the last update kernel and how many of its draws ended at the attempt cap
+ * NOT BUILT: a != 1 or b != 1/2; joint-block draws; float64 states; several ranks; a math_mode = fast variant; populations on
+ * different devices. */
+typedef struct viprs_csx viprs_csx;
+enum viprs_csx_buffer { VIPRS_CSX_PSI = 0, VIPRS_CSX_DELTA = 1, VIPRS_CSX_ATTEMPTS = 2, VIPRS_CSX_BUFFER_COUNT = 3 };
+#define VIPRS_CSX_MAX_POP 8
+#define VIPRS_CSX_MAX_ATTEMPTS 32
+#define VIPRS_N_CSX_SUMS 2
+int viprs_csx_create(viprs_csx** out, int n_pop, viprs_state* const* states, int64_t m_union, const int64_t* row_of);
+int viprs_csx_destroy(viprs_csx* x);
+int viprs_csx_update(viprs_csx* x, int n, const double* params, double psi_max, uint64_t seed, uint64_t draw_index, int flags,
+                     int sync);
+int viprs_csx_sums(viprs_csx* x, int n, const int32_t* cols, double* out);
+int viprs_csx_upload(viprs_csx* x, int which, const void* host);
+int viprs_csx_download(viprs_csx* x, int which, void* host);
+int viprs_csx_last(viprs_csx* x, double* ms, int64_t* n_capped);
+
 /* ---- SBayesR: a mixture Gibbs draw where the mixture E-step takes an expectation ---------------------------------------------
  * SBayesR (Lloyd-Jones et al. 2019; GCTB --sbayes R) samples every effect from its conditional posterior under a finite mixture
  * of normals with a point mass at zero: component k = 1..K has prior variance gamma_k sigma2_beta and weight pi_k, component 0

@@ -38,6 +38,8 @@ GIBBS_KEEP_DRAWS = 1
 CS_PSI, CS_DELTA, CS_UB, CS_Z1, CS_Z2, CS_E = range(6)   # viprs_cs_buffer
 CS_KEEP_VARIATES, CS_PREPARE_ONLY = 1, 2
 N_CS_SUMS = 4
+CSX_PSI, CSX_DELTA, CSX_ATTEMPTS = range(3)              # viprs_csx_buffer
+CSX_MAX_POP, CSX_MAX_ATTEMPTS, N_CSX_SUMS = 8, 32, 2
 PANEL_BAYESR, BAND_BAYESR = 6, 5                    # ... of the SBayesR route (viprs_bayesr_route)
 BAYESR_UNIF, BAYESR_Z, BAYESR_KSTAR, BAYESR_MEAN_SUM, BAYESR_PIP_SUM = range(5)   # viprs_bayesr_buffer
 BAYESR_KEEP_DRAWS = 1
@@ -166,6 +168,13 @@ _PROTOS = {
     "viprs_state_cs_upload": (_i, [_vp, _i, _vp]),
     "viprs_state_cs_download": (_i, [_vp, _i, _vp]),
     "viprs_plan_last_cs_ms": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_d)]),
+    "viprs_csx_create": (_i, [ctypes.POINTER(_vp), _i, ctypes.POINTER(_vp), _i64, _vp]),
+    "viprs_csx_destroy": (_i, [_vp]),
+    "viprs_csx_update": (_i, [_vp, _i, _vp, _d, _u64, _u64, _i, _i]),
+    "viprs_csx_sums": (_i, [_vp, _i, _vp, _vp]),
+    "viprs_csx_upload": (_i, [_vp, _i, _vp]),
+    "viprs_csx_download": (_i, [_vp, _i, _vp]),
+    "viprs_csx_last": (_i, [_vp, ctypes.POINTER(_d), _pi64]),
     "viprs_plan_dot": (_i, [_vp, _i, _i, _vp, _vp, _d, _i]),
     "viprs_state_dot": (_i, [_vp, _i, _d, _i, _vp]),
     "viprs_plan_last_dot_ms": (_i, [_vp, ctypes.POINTER(_d)]),

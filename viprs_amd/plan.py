@@ -1121,3 +1121,70 @@ class DeviceState:
 
     def synchronize(self):
         L.check(L.lib.viprs_state_synchronize(self._h))
+
+
+class DeviceCoupling:
+    """The PRS-CSx coupling of P float32 grid `DeviceState`s of one width through one local scale per SNP of the union of
+    their SNP sets (`viprs_csx_*`, include/viprs_hip.h; `viprs_amd.stats.csx` is the host definition).  `row_of`: ``(P,
+    m_union)`` int64, the row of every union SNP in each state's plan or -1.  The states stay the caller's; the coupling
+    keeps them alive."""
+
+    _BUF = {"psi": (L.CSX_PSI, np.float32), "delta": (L.CSX_DELTA, np.float32), "attempts": (L.CSX_ATTEMPTS, np.uint8)}
+
+    def __init__(self, states, row_of):
+        self.states = list(states)
+        r = np.ascontiguousarray(row_of, dtype=np.int64)
+        if r.ndim != 2 or r.shape[0] != len(self.states):
+            raise ValueError("row_of: an int64 array of shape (len(states), m_union)")
+        self.n_pop, self.m_union = int(r.shape[0]), int(r.shape[1])
+        self.width = int(self.states[0].width) if self.states else 0
+        hs = (ctypes.c_void_p * max(self.n_pop, 1))(*[s._h for s in self.states])
+        self._h = ctypes.c_void_p()
+        L.check(L.lib.viprs_csx_create(ctypes.byref(self._h), self.n_pop, hs, self.m_union, _ptr(r)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            L.lib.viprs_csx_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, params, psi_max=1.0, seed=0, draw_index=0, keep_variates=False, prepare_only=False, sync=True):
+        """One coupled update for the chains of `params` -- rows ``(column, phi, sigma2_0 .. sigma2_{P-1})``: new shared
+        ``psi`` and ``delta``, scattered with ``mu_mult``, ``half_var_tau``, ``u_logs`` into every state (`viprs_csx_update`)."""
+        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 2 + self.n_pop)
+        flags = (L.CS_KEEP_VARIATES if keep_variates else 0) | (L.CS_PREPARE_ONLY if prepare_only else 0)
+        L.check(L.lib.viprs_csx_update(self._h, int(p.shape[0]), _ptr(p), float(psi_max), int(seed), int(draw_index), flags,
+                                       int(bool(sync))))
+
+    def sums(self, cols=None):
+        """``(n, 2)`` float64, one row per listed column (default: every column): sum delta, sum psi over the union."""
+        c = None if cols is None else np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32)
+        n = self.width if c is None else int(c.shape[0])
+        out = np.zeros((n, L.N_CSX_SUMS), dtype=np.float64)
+        L.check(L.lib.viprs_csx_sums(self._h, n, None if c is None else _ptr(c), _ptr(out)))
+        return out
+
+    def download(self, which):
+        """``"psi"``, ``"delta"`` (float32) or ``"attempts"`` (uint8): ``(m_union, G)`` column-major."""
+        code, dt = self._BUF[which]
+        out = np.zeros((self.m_union, self.width), dtype=dt, order="F")
+        L.check(L.lib.viprs_csx_download(self._h, code, _ptr(out)))
+        return out
+
+    def upload(self, which, array):
+        code, dt = self._BUF[which]
+        a = np.asarray(array)
+        if a.dtype != dt or a.shape != (self.m_union, self.width) or not a.flags.f_contiguous:
+            raise ValueError(f"{which}: a Fortran-contiguous {np.dtype(dt).name} array of shape {(self.m_union, self.width)}")
+        L.check(L.lib.viprs_csx_upload(self._h, code, _ptr(a)))
+
+    def last(self):
+        """``(ms, n_capped)`` of the last update: its event time and the draws that ended at the attempt cap."""
+        ms, nc = ctypes.c_double(0.0), ctypes.c_int64(0)
+        L.check(L.lib.viprs_csx_last(self._h, ctypes.byref(ms), ctypes.byref(nc)))
+        return ms.value, int(nc.value)
